@@ -14,12 +14,31 @@ partition per GPU (N = 1: the plain hip-executor algorithms; N > 1: segment
 totals/carries exchanged with one RCCL all-gather of 8 B per GPU).
 value = algorithmic bytes of all GPUs / max-over-ranks wall time of K steps.
 
-Also reported (outside the timed region, rank 0): sort of 2^30 uint64 keys
-(56 B/key executed by the hybrid path; 136 B/key for the 8-pass LSD), copy_if, f64 reduce/scan, the 1d_stencil heat
-solver, the per-kernel HIP-event timings, the roofline of the dominant
-kernel, and the HPX-par host baseline (oracle restatement) on a 2^27 sample.
+A plain run sets up, warms up, times the K steps, writes the outputs of the
+last step if --dump-outputs is given, and prints the JSON line (`ms_per_step`
+is the wall time of one timed step).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]
+--dump-outputs DIR: what the last timed step returned to its caller, as
+float64 .npy files: triad.npy (a), inclusive_scan.npy (y) and
+transform_reduce.npy (the sum, one element).  The inputs are generated from
+fixed seeds, so two runs with the same arguments compare file for file.  An
+array of more than 2^21 elements is sampled: its first and last 4096 elements
+and 510 windows of 4096 at seeded positions between them, in index order
+(dump_windows; 16 MiB per array).  With N > 1 ranks each rank writes its own
+partition as <name>.rank<r>.npy.
+
+--full adds (outside the timed region, rank 0): sort of 2^30 uint64 keys
+(56 B/key executed by the hybrid path; 136 B/key for the 8-pass LSD), copy_if, f64 reduce/scan, the 1d_stencil heat
+solver, the measured HBM traffic of the dominant kernel (roofline.traffic, a
+rocprofv3 PMC pass), and the HPX-par host baseline (oracle restatement) on a
+2^27 sample.  The per-kernel HIP-event timings and the roofline's achieved
+rate come from events recorded inside the timed steps and are always reported.
+
+--full also runs the self-checks of the step (scan-last == reduce, triad
+samples against the oracle); --no-cpu, --no-extras and --no-pmc drop parts of
+it.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 `--gpus N` (N > 1) without torchrun starts the N ranks itself (launch_ranks);
 a WORLD_SIZE that differs from --gpus is an error.  The JSON line carries
@@ -147,6 +166,10 @@ def main(argv=None, comm_tgt=None):
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--logn", type=int, default=30)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the self-checks, the extras, the CPU baseline and the PMC traffic pass")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--cpu-logn", type=int, default=27)
@@ -160,6 +183,8 @@ def main(argv=None, comm_tgt=None):
     # their environment (tests/test_bench_launcher.py)
     ap.add_argument("--launch-probe", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.triad_only:
         return triad_only(args.logn)
     if comm_tgt is None:
@@ -240,15 +265,11 @@ def main(argv=None, comm_tgt=None):
     k_reduce = np.mean([ev.ms(m[1], m[2]) for m in marks])
     k_scan = np.mean([ev.ms(m[2], m[3]) for m in marks])
 
-    # cheap self-check: last inclusive-scan value == reduce result (int64 exact)
-    if len(y.local) and rank == world - 1:
-        last_local = y.local[len(y.local) - 1]
-        assert last_local == r, f"scan/reduce mismatch {last_local} != {r}"
-    from oracle import oracle as O  # checker only
-    for i in [0, 1, n_local // 3, n_local - 1]:
-        bb = O.generate(np.float64, "unit", 1, 1, offset=a.lo + i)[0]
-        cc = O.generate(np.float64, "unit", 1, 2, offset=a.lo + i)[0]
-        assert a.local[i] == bb + cc * 3.0, "triad parity"
+    if args.dump_outputs:
+        dump_outputs(L, tgt, args.dump_outputs, "" if world == 1 else f".rank{rank}",
+                     {"triad": a.local, "inclusive_scan": y.local}, {"transform_reduce": r})
+    if args.full:
+        check_step(a, y, r, n_local, rank, world)
 
     bytes_step = (24 + 8 + 16) * n_local
     value = world * bytes_step * args.steps / elapsed / 1e9
@@ -286,16 +307,17 @@ def main(argv=None, comm_tgt=None):
     # HPXHIP_RCCL_SELF=1 (one rank through TorchComm under torchrun): the
     # N > 1 rows instead, as a rehearsal of the 8-GPU run on one GPU
     rehearse = world == 1 and os.environ.get("HPXHIP_RCCL_SELF") == "1"
-    if not args.no_extras and world == 1 and not rehearse:
+    extras_on = args.full and not args.no_extras
+    if extras_on and world == 1 and not rehearse:
         out["extras"] = extras(hpx, L, ex, F, S, comm, tgt, pol, x, y, n_local, world, args)
     y.local.free()
-    if not args.no_extras and (world > 1 or rehearse):
+    if extras_on and (world > 1 or rehearse):
         out["extras"] = dist_extras(S, F, comm, tgt, pol, x, n_local, world, args)
     else:
         x.local.free()
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(args.cpu_logn)
-    if rank == 0 and world == 1 and not args.no_pmc:
+    if args.full and rank == 0 and world == 1 and not args.no_pmc:
         traffic, detail = pmc_traffic(args.logn)
         out["roofline"]["traffic"] = traffic
         out["roofline"]["traffic_detail"] = detail
@@ -306,6 +328,55 @@ def main(argv=None, comm_tgt=None):
         import torch.distributed as dist
         if dist.is_initialized():
             dist.destroy_process_group()
+
+
+def check_step(a, y, r, n_local, rank, world):
+    """Self-checks of the last step (--full): the last inclusive-scan value ==
+    the reduce result (int64 exact), and triad samples against the oracle."""
+    if len(y.local) and rank == world - 1:
+        last_local = y.local[len(y.local) - 1]
+        assert last_local == r, f"scan/reduce mismatch {last_local} != {r}"
+    from oracle import oracle as O  # checker only
+    for i in [0, 1, n_local // 3, n_local - 1]:
+        bb = O.generate(np.float64, "unit", 1, 1, offset=a.lo + i)[0]
+        cc = O.generate(np.float64, "unit", 1, 2, offset=a.lo + i)[0]
+        assert a.local[i] == bb + cc * 3.0, "triad parity"
+
+
+DUMP_WINDOW = 4096    # elements per sampled window
+DUMP_WINDOWS = 510    # seeded windows between the first and the last
+DUMP_SEED = 0xD0E5
+
+
+def dump_windows(n):
+    """[(first index, count), ...] of the elements --dump-outputs keeps of an
+    n-element array: all of it up to 2^21 elements, else the first and the
+    last DUMP_WINDOW elements and DUMP_WINDOWS windows at seeded positions,
+    in index order (the same for every run and every build)."""
+    if n <= (DUMP_WINDOWS + 2) * DUMP_WINDOW:
+        return [(0, n)]
+    starts = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n - DUMP_WINDOW, DUMP_WINDOWS))
+    return [(0, DUMP_WINDOW)] + [(int(s), DUMP_WINDOW) for s in starts] + [(n - DUMP_WINDOW, DUMP_WINDOW)]
+
+
+def dump_outputs(L, tgt, directory, suffix, vectors, scalars):
+    """--dump-outputs: DIR/<name><suffix>.npy (float64) for each device vector
+    (the windows of dump_windows, copied to the host after the timed steps)
+    and each scalar result (one element)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, vec in vectors.items():
+        wins = dump_windows(len(vec))
+        host = np.empty(sum(c for _, c in wins), np.dtype(L.DTYPE_NAME[vec.dtype]))
+        pos = 0
+        for lo, c in wins:
+            if c:
+                L.call("hpxhip_memcpy_async", ctypes.c_void_p(host.ctypes.data + pos * vec.value_size),
+                       ctypes.c_void_p(vec.data() + lo * vec.value_size), c * vec.value_size, L.D2H, tgt.stream)
+            pos += c
+        tgt.synchronize()
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), host.astype(np.float64))
+    for name, v in scalars.items():
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.array([v], np.float64))
 
 
 def timed(L, tgt, fn, reps=3):

@@ -57,6 +57,22 @@ def test_world_size_mismatch_is_an_error():
     assert "WORLD_SIZE=2" in r.stderr and r.stdout.strip() == ""
 
 
+def test_dump_windows_fixed_bounded_sample():
+    """--dump-outputs keeps whole small arrays and a fixed sample of large
+    ones: inside the array, in index order, head and tail included, the same
+    on every call, and two 2^30-element arrays stay far below 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_windows(0) == [(0, 0)] and bench.dump_windows(1000) == [(0, 1000)]
+    assert bench.dump_windows(1 << 21) == [(0, 1 << 21)]
+    for n in ((1 << 21) + 1, 1 << 30):
+        w = bench.dump_windows(n)
+        assert w == bench.dump_windows(n)
+        assert w[0][0] == 0 and w[-1][0] + w[-1][1] == n
+        assert all(0 <= lo and lo + c <= n for lo, c in w) and [lo for lo, _ in w] == sorted(lo for lo, _ in w)
+        assert 2 * 8 * sum(c for _, c in w) + 8 <= 40 << 20
+
+
 def test_launcher_never_imports_the_library():
     """The launcher path returns before `import hpx_amd`: run main() in a
     child with the library import poisoned and a fake torch.distributed.run

@@ -27,7 +27,7 @@ def _worker(rank, size, port, q):
         comm = HostStagedComm(tgt)
         out = io.StringIO()
         with contextlib.redirect_stdout(out):
-            bench.main(["--gpus", str(size), "--steps", "2", "--warmup", "1", "--logn", "22", "--no-cpu",
+            bench.main(["--gpus", str(size), "--steps", "2", "--warmup", "1", "--logn", "22", "--full", "--no-cpu",
                         "--no-pmc", "--stencil-logn", "22", "--stencil-steps", "40"], comm_tgt=(comm, tgt))
         q.put((rank, out.getvalue()))
     except Exception as e:

@@ -17,6 +17,8 @@ calls one whole-algorithm entry point of the C ABI (include/hpxhip.h):
   transform_inclusive_scan   transform_inclusive_scan.hpp:320/445
   transform_exclusive_scan   transform_exclusive_scan.hpp:317
   sort / sort_by_key         sort.hpp:364, sort_by_key.hpp:42-78
+  reduce_by_key              reduce_by_key.hpp:586 (one pass instead of the
+                             reference's three, :294-411)
   generate (splitmix/iota)   generate.hpp (device generator functors)
   for_loop / for_loop_n      for_loop.hpp:808; for_loop_strided 604,
   for_loop_n_strided         1014 (inductions: for_loop_induction.hpp;
@@ -399,6 +401,40 @@ def sort_by_key(pol, key_first, key_last, value_first, comp=F.less):
     return _finish(is_task, stream, tgt, lambda: (key_last, value_first + n))
 
 
+def reduce_by_key(pol, key_first, key_last, values_first, keys_output, values_output, comp=None, func=F.plus):
+    """reduce_by_key.hpp:586: every run of consecutive equal keys gives one
+    output pair (the run's first key, its values folded left to right with
+    func); returns (keys_output + count, values_output + count), or its
+    future under par(task).  comp is std::equal_to (None or F.key_equal),
+    func an associative F.BinaryOp.  The outputs may be the inputs (exactly
+    aliased).  Unlike the reference, n <= 1 returns the ends of what was
+    written (+0, +1) rather than the un-advanced iterators, and only count
+    elements of values_output are written (the reference scans into all n)."""
+    _exec_of(pol)
+    if comp is not None:
+        F.require(comp, F.KeyCompare, "reduce_by_key")
+    func = F.require(func, F.BinaryOp, "reduce_by_key")
+    n = _check_range(key_first, key_last)
+    for it in (values_first, keys_output, values_output):
+        if not isinstance(it, iterator):
+            raise TypeError("reduce_by_key: expected device iterators (hpx_amd.compute.iterator)")
+    if key_first.dtype != keys_output.dtype:
+        raise TypeError("reduce_by_key: key input and output dtypes differ")
+    if values_first.dtype != values_output.dtype:
+        raise TypeError("reduce_by_key: value input and output dtypes differ")
+    stream, tgt, is_task = _context(pol, key_first, values_first, keys_output, values_output)
+    dev, host = _slots_for(tgt).next()
+    L.call("hpxhip_reduce_by_key", key_first.dtype, values_first.dtype, func.kind, _vp(key_first.address),
+           _vp(values_first.address), _vp(keys_output.address), _vp(values_output.address), n, _vp(dev), stream,
+           None, 0)
+    L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8, L.D2H, stream)
+
+    def ends():
+        count = _read_host(host, L.U64)
+        return keys_output + count, values_output + count
+    return _finish(is_task, stream, tgt, ends)
+
+
 def merge(pol, first1, last1, first2, last2, dest, comp=F.less):
     """merge.hpp:476: stable merge of two sorted ranges into dest (equal keys:
     the first range's first, merge.hpp:52-80); returns the tagged tuple
@@ -701,7 +737,7 @@ def _guarded(fn):
 
 for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "copy_n", "copy_if", "transform",
               "reduce", "transform_reduce", "inclusive_scan", "exclusive_scan", "transform_inclusive_scan",
-              "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "merge", "for_loop_n", "for_loop",
+              "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge", "for_loop_n", "for_loop",
               "for_loop_n_strided", "for_loop_strided"):
     if _name in globals():
         globals()[_name] = _guarded(globals()[_name])

@@ -1,4 +1,5 @@
-// scan.hip -- inclusive_scan / exclusive_scan / transform_{in,ex}clusive_scan.
+// scan.hip -- inclusive_scan / exclusive_scan / transform_{in,ex}clusive_scan,
+// and reduce_by_key (the segmented look-back, at the end of this file).
 //
 // Reference: inclusive_scan.hpp:90-173 and exclusive_scan.hpp:100-175 run
 // scan_partitioner.hpp:62-156 on the host -- three phases, the data read
@@ -16,8 +17,11 @@
 //             prefix and stored with 16-B stores.
 // Integer results are exact; FP results follow a tree order that can differ
 // from the sequential left fold (tolerance in DESIGN.md).
+#include <cstdlib>
+
 #include "internal.hpp"
 #include <hpxhip/kernels/lookback.hpp>
+#include <hpxhip/kernels/reduce_by_key_kernel.hpp>
 #include <hpxhip/kernels/scan_kernel.hpp>
 
 using namespace hpxhip;
@@ -155,6 +159,145 @@ size_t scan_scratch_bytes(int dtype, uint64_t n) {
     return dtype_size(dtype) == 8 ? scratch_total<uint64_t>(n) : scratch_total<uint32_t>(n);
 }
 }  // namespace hpxhip
+
+// ------------------------------------------------------------ reduce_by_key
+// reduce_by_key.hpp:586 -- one pass (reduce_by_key_kernel.hpp): head flags
+// from the keys in registers, a segmented fold in the tile, the composite
+// {runs closed, boundary seen, open partial} through the fixed-association
+// look-back, one (key, value) written per run.  Scratch: [256 B | tile
+// slots], the slots zeroed per call.
+namespace {
+
+namespace rbk = hpxhip::reduce_by_key_detail;
+
+struct key_equal {
+    template <typename K>
+    __device__ __forceinline__ bool operator()(K a, K b) const {
+        return a == b;
+    }
+};
+
+template <typename K, typename V>
+size_t rbk_state_bytes(uint64_t n, bool state64) {
+    const uint64_t ntiles = rbk::ntiles_for<K, V>(n);
+    const size_t per = state64 ? rbk::state_t<uint64_t, V>::bytes_per_tile() : rbk::state_t<uint32_t, V>::bytes_per_tile();
+    return align_up(kSlotsOff + ntiles * per, 256);
+}
+
+template <typename K, typename V, typename CT, typename F>
+int launch_reduce_by_key_ct(const K* keys, const V* vals, K* keys_out, V* vals_out, uint64_t n, F f,
+                            uint64_t* count_dev, char* ws, hipStream_t s) {
+    constexpr int E = rbk::lane_elems<K, V>();
+    const uint64_t ntiles = rbk::ntiles_for<K, V>(n);
+    HPXHIP_CHECK(hipMemsetAsync(ws, 0, rbk_state_bytes<K, V>(n, sizeof(CT) == 8), s));
+    rbk::state_t<CT, V> st{reinterpret_cast<uint64_t*>(ws + kSlotsOff), device_error_word(s)};
+    // the vector path: both inputs aligned for E-element loads
+    const int vec_ok = reinterpret_cast<uintptr_t>(keys) % (E * sizeof(K)) == 0 &&
+                       reinterpret_cast<uintptr_t>(vals) % (E * sizeof(V)) == 0;
+    hipLaunchKernelGGL((rbk::k_reduce_by_key<K, V, key_equal, F, CT>), dim3(static_cast<unsigned>(ntiles)),
+                       dim3(rbk::kThreads), 0, s, keys, vals, keys_out, vals_out, n, key_equal{}, f, count_dev, st,
+                       vec_ok);
+    HPXHIP_CHECK_LAUNCH();
+    return 0;
+}
+
+// The run count travels as 32 bits below 2^32 elements;
+// HPXHIP_REDUCE_BY_KEY_STATE64=1 forces the 64-bit form at any n (tests;
+// read per call).
+template <typename K, typename V, typename F>
+int launch_reduce_by_key(const void* keys, const void* vals, void* keys_out, void* vals_out, uint64_t n, F f,
+                         uint64_t* count_dev, hipStream_t s, void* scratch, size_t scratch_bytes) {
+    const char* e = getenv("HPXHIP_REDUCE_BY_KEY_STATE64");
+    const bool state64 = (e && e[0] == '1') || n >= (uint64_t{1} << 32);
+    void* ws = nullptr;
+    int rc = resolve_scratch(s, scratch, scratch_bytes, rbk_state_bytes<K, V>(n, state64), &ws);
+    if (rc) return rc;
+    const K* kp = static_cast<const K*>(keys);
+    const V* vp = static_cast<const V*>(vals);
+    K* ko = static_cast<K*>(keys_out);
+    V* vo = static_cast<V*>(vals_out);
+    char* base = static_cast<char*>(ws);
+    if (state64) return launch_reduce_by_key_ct<K, V, uint64_t>(kp, vp, ko, vo, n, f, count_dev, base, s);
+    return launch_reduce_by_key_ct<K, V, uint32_t>(kp, vp, ko, vo, n, f, count_dev, base, s);
+}
+
+// Keys only need size and equality: the integers of one width share a
+// bitwise class, floats compare by value (-0.0 == +0.0, NaN != NaN).
+template <typename F>
+int with_key_class(int key_dtype, F&& f) {
+    switch (key_dtype) {
+        case HPXHIP_I32:
+        case HPXHIP_U32: return f(tag<uint32_t>{});
+        case HPXHIP_I64:
+        case HPXHIP_U64: return f(tag<uint64_t>{});
+        case HPXHIP_F32: return f(tag<float>{});
+        case HPXHIP_F64: return f(tag<double>{});
+        default: return HPXHIP_ERROR_INVALID_ARGUMENT;
+    }
+}
+
+// Signed integer values only reach here for MIN / MAX: the wrapping and
+// bitwise operators give the same bits on the unsigned type of the width
+// (hpxhip_reduce_by_key), which keeps the kernel count down.
+template <typename V, typename F>
+int with_value_op(int op, F&& f) {
+    if constexpr (std::is_integral_v<V> && std::is_signed_v<V>) {
+        switch (op) {
+            case HPXHIP_MIN: return f(op_min{});
+            case HPXHIP_MAX: return f(op_max{});
+            default: return HPXHIP_ERROR_INVALID_ARGUMENT;
+        }
+    } else {
+        return with_binop<V>(op, f);
+    }
+}
+
+__global__ void k_zero_u64(uint64_t* c) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *c = 0;
+}
+
+}  // namespace
+
+namespace hpxhip {
+size_t reduce_by_key_scratch_bytes(int key_dtype, int value_dtype, uint64_t n) {
+    // the 64-bit run count, the smaller tile (8-byte keys): covers every launch
+    (void)key_dtype;
+    return dtype_size(value_dtype) == 8 ? rbk_state_bytes<uint64_t, uint64_t>(n, true)
+                                        : rbk_state_bytes<uint64_t, uint32_t>(n, true);
+}
+}  // namespace hpxhip
+
+extern "C" int hpxhip_reduce_by_key(int key_dtype, int value_dtype, int op, const void* keys_in,
+                                    const void* values_in, void* keys_out, void* values_out, uint64_t n,
+                                    uint64_t* count_dev, hpxhip_stream stream, void* scratch, size_t scratch_bytes) {
+    HPXHIP_ANNOTATE("hpxhip_reduce_by_key");
+    if (!count_dev || (n && (!keys_in || !values_in || !keys_out || !values_out)))
+        return HPXHIP_ERROR_INVALID_ARGUMENT;
+    if (dtype_size(key_dtype) == 0 || dtype_size(value_dtype) == 0) return HPXHIP_ERROR_INVALID_ARGUMENT;
+    if (op < HPXHIP_PLUS || op > HPXHIP_BIT_XOR) return HPXHIP_ERROR_INVALID_ARGUMENT;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    device_guard g(s);
+    if (g.status) return g.status;
+    if (n == 0) {
+        hipLaunchKernelGGL(k_zero_u64, dim3(1), dim3(64), 0, s, count_dev);
+        HPXHIP_CHECK_LAUNCH();
+        return 0;
+    }
+    if (op != HPXHIP_MIN && op != HPXHIP_MAX) {
+        if (value_dtype == HPXHIP_I32) value_dtype = HPXHIP_U32;
+        if (value_dtype == HPXHIP_I64) value_dtype = HPXHIP_U64;
+    }
+    return with_key_class(key_dtype, [&](auto kt) -> int {
+        using K = typename decltype(kt)::type;
+        return with_dtype(value_dtype, [&](auto vt) -> int {
+            using V = typename decltype(vt)::type;
+            return with_value_op<V>(op, [&](auto o) -> int {
+                return launch_reduce_by_key<K, V>(keys_in, values_in, keys_out, values_out, n, o, count_dev, s,
+                                                  scratch, scratch_bytes);
+            });
+        });
+    });
+}
 
 extern "C" int hpxhip_scan(int dtype, int op, int inclusive, int conv_kind, const void* conv_scalars,
                            const void* init, const void* prefix_dev, const void* in, void* out, uint64_t n,

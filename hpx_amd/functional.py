@@ -274,6 +274,22 @@ less = Compare(False, "std::less")
 greater = Compare(True, "std::greater")
 
 
+@dataclass(frozen=True)
+class KeyCompare:
+    """The key comparator of reduce_by_key (reduce_by_key.hpp:586, ``comp``):
+    two neighbouring keys belong to one run when it holds."""
+    name: str
+
+    def __call__(self, a, b):
+        return a == b
+
+
+# std::equal_to<>: integers by their bits, floats by value (-0.0 == +0.0 is
+# one run, every NaN a run of its own).  Not ``equal_to``: that names the
+# predicate ``x == a`` of copy_if.
+key_equal = KeyCompare("std::equal_to")
+
+
 def require(obj, cls, what: str):
     if not isinstance(obj, cls):
         raise TypeError(

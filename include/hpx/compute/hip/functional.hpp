@@ -12,6 +12,7 @@
 //   traits::binop<F>   -> HPXHIP_*     (reduce / scan operators)
 //   traits::pred<F>    -> HPXHIP_P_*   (copy_if)
 //   traits::compare<F> -> ascending / descending (sort, sort_by_key)
+//   traits::key_equal<F> -> std::equal_to (reduce_by_key's key comparator)
 //
 // A user functor with the same meaning as a built-in one opts in by
 // specialising the trait, e.g. the STREAM benchmark's own
@@ -171,6 +172,7 @@ template <typename F, typename Enable = void> struct binary;
 template <typename F, typename Enable = void> struct binop;
 template <typename F, typename Enable = void> struct pred;
 template <typename F, typename Enable = void> struct compare;
+template <typename F, typename Enable = void> struct key_equal;
 
 namespace detail {
 template <int K>
@@ -250,11 +252,15 @@ HPXHIP_PRED_TRAIT(any_bits, HPXHIP_P_BITS)
 template <typename T> struct compare<std::less<T>> { static constexpr bool descending = false; };
 template <typename T> struct compare<std::greater<T>> { static constexpr bool descending = true; };
 
+// reduce_by_key's comp: std::equal_to<T> and std::equal_to<> (= equal_to<void>)
+template <typename T> struct key_equal<std::equal_to<T>> {};
+
 template <typename F> using unary_t = unary<typename std::decay<F>::type>;
 template <typename F> using binary_t = binary<typename std::decay<F>::type>;
 template <typename F> using binop_t = binop<typename std::decay<F>::type>;
 template <typename F> using pred_t = pred<typename std::decay<F>::type>;
 template <typename F> using compare_t = compare<typename std::decay<F>::type>;
+template <typename F> using key_equal_t = key_equal<typename std::decay<F>::type>;
 
 // Arithmetic type of a transform: the trait's compute_type, else the
 // functor's (triad_step<double> over int vectors computes in double,

@@ -17,6 +17,7 @@
 //   transform_exclusive_scan     transform_exclusive_scan.hpp:317
 //   sort                         sort.hpp:364                 -> RandomIt
 //   sort_by_key                  sort_by_key.hpp:125          -> tagged_pair<keys, values>
+//   reduce_by_key                reduce_by_key.hpp:586        -> pair<keys_out, values_out>
 //
 // Synchronous policies (seq, par, par_unseq) return the value after the
 // target's stream is synchronised (the reference's bulk_sync_execute,
@@ -774,6 +775,64 @@ detail::result_t<P, util::tagged_pair<KeyIt, ValIt>> sort_by_key(P&& p, KeyIt ke
     return detail::finish<R>(p, t, [key_last, vend] { return R{key_last, vend}; });
 }
 
+// ---------------------------------------------------------- reduce_by_key
+// reduce_by_key.hpp:586: every run of consecutive keys that comp equates
+// gives keys_output[j] = the run's first key and values_output[j] = its
+// values folded left to right with func (associative; it need not commute
+// and needs no identity).  Returns the ends of the two outputs as a plain
+// std::pair (the reference's result here is not a tagged one).  One pass
+// (hpxhip/kernels/reduce_by_key_kernel.hpp) instead of the reference's key
+// states, tuple scan and zipped copy_if (:294-411).  The outputs may be the
+// inputs (keys_output == key_first, values_output == values_first, as the
+// reference's test runs it).  std::equal_to with a std:: operator runs the
+// library's kernels; any other HPX_HOST_DEVICE comp / func runs the same
+// kernel as a device closure (hipcc).
+// Two deliberate differences from the reference:
+//  - n <= 1: the reference returns the un-advanced output iterators (and at
+//    n == 0 dereferences empty ranges, :604-609, its FIXME at :302); here the
+//    result is the ends of what was written, +0 for n == 0, +1 for n == 1.
+//  - values_output only needs room for the runs: the reference scans into it
+//    over all n positions before compacting, so its callers size it for n.
+template <typename P, typename KeyIt, typename ValIt, typename KeyOut, typename ValOut,
+          typename Comp = std::equal_to<detail::value_t<KeyIt>>, typename Func = std::plus<detail::value_t<ValIt>>>
+detail::result_t<P, std::pair<KeyOut, ValOut>> reduce_by_key(P&& p, KeyIt key_first, KeyIt key_last,
+                                                             ValIt values_first, KeyOut keys_output,
+                                                             ValOut values_output, Comp&& comp = Comp(),
+                                                             Func&& func = Func()) {
+    static_assert(detail::is_dev<KeyIt> && detail::is_dev<ValIt> && detail::is_dev<KeyOut> && detail::is_dev<ValOut>,
+                  "reduce_by_key: device iterators required");
+    using K = detail::value_t<KeyIt>;
+    using V = detail::value_t<ValIt>;
+    static_assert(std::is_same<K, detail::value_t<KeyOut>>::value && std::is_same<V, detail::value_t<ValOut>>::value,
+                  "reduce_by_key: the outputs hold the inputs' value types");
+    using R = std::pair<KeyOut, ValOut>;
+    auto const& t = detail::target_of(p, key_first);
+    uint64_t n = detail::distance(key_first, key_last);
+    auto slot = t.make_result_slot();
+    constexpr bool mapped_comp = detail::tr::detail::is_complete<detail::tr::key_equal_t<Comp>>::value;
+    if constexpr (mapped_comp && detail::tr::is_binop<Func>) {
+        detail::check(hpxhip_reduce_by_key(detail::dt<K>, detail::dt<V>, detail::tr::binop_t<Func>::kind,
+                                           key_first.device_ptr(), values_first.device_ptr(),
+                                           keys_output.device_ptr(), values_output.device_ptr(), n,
+                                           static_cast<uint64_t*>(slot.device()), t.stream(), nullptr, 0),
+                      "reduce_by_key");
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::reduce_by_key(t, static_cast<K const*>(key_first.device_ptr()),
+                                   static_cast<V const*>(values_first.device_ptr()), keys_output.device_ptr(),
+                                   values_output.device_ptr(), n, comp, func, static_cast<uint64_t*>(slot.device()));
+#else
+        detail::no_device_mapping<std::conditional_t<mapped_comp, Func, Comp>>("reduce_by_key");
+#endif
+    }
+    detail::fetch_slot(t, slot, 8, "reduce_by_key count");
+    return detail::finish_slot<R>(p, t, std::move(slot), [keys_output, values_output](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return R{keys_output + static_cast<std::ptrdiff_t>(c), values_output + static_cast<std::ptrdiff_t>(c)};
+    });
+}
+
 // ------------------------------------------------------------------ merge
 // merge.hpp:476: stable (first range first on ties), ascending / descending.
 template <typename P, typename In1, typename In2, typename Out, typename Comp = std::less<>>
@@ -1178,6 +1237,7 @@ HPXHIP_GUARDED_ALGORITHM(transform_exclusive_scan)
 HPXHIP_GUARDED_ALGORITHM(sort)
 HPXHIP_GUARDED_ALGORITHM(is_sorted)
 HPXHIP_GUARDED_ALGORITHM(sort_by_key)
+HPXHIP_GUARDED_ALGORITHM(reduce_by_key)
 HPXHIP_GUARDED_ALGORITHM(merge)
 HPXHIP_GUARDED_ALGORITHM(for_loop_n)
 HPXHIP_GUARDED_ALGORITHM(for_loop)
@@ -1214,6 +1274,7 @@ using parallel::v1::reduction_plus;
 using parallel::v1::merge;
 using parallel::v1::inclusive_scan;
 using parallel::v1::reduce;
+using parallel::v1::reduce_by_key;
 using parallel::v1::is_sorted;
 using parallel::v1::sort;
 using parallel::v1::sort_by_key;

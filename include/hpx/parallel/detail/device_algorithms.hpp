@@ -14,6 +14,7 @@
 //   scans                      scan_kernel.hpp     (single pass, decoupled
 //                                                   look-back, 16-B tiles)
 //   copy_if                    copy_if_kernel.hpp  (ballot ranks, look-back)
+//   reduce_by_key              reduce_by_key_kernel.hpp (segmented look-back)
 //   sort (comp, proj)          merge_kernel.hpp    (block sort in LDS, then
 //                                                   merge-path passes)
 //
@@ -42,6 +43,7 @@
 #if HPX_HAVE_HIP_DEVICE_CLOSURES
 #include <hpxhip/kernels/copy_if_kernel.hpp>
 #include <hpxhip/kernels/merge_kernel.hpp>
+#include <hpxhip/kernels/reduce_by_key_kernel.hpp>
 #include <hpxhip/kernels/reduce_kernel.hpp>
 #include <hpxhip/kernels/scan_kernel.hpp>
 #endif
@@ -277,6 +279,61 @@ void copy_if(compute::hip::target const& t, T const* in, T* out, uint64_t n, Pre
     else if (aligned) copy_if_launch<T, P, true, uint64_t>(t, in, out, n, P{pred}, count_dev);
     else if (small) copy_if_launch<T, P, false, uint32_t>(t, in, out, n, P{pred}, count_dev);
     else copy_if_launch<T, P, false, uint64_t>(t, in, out, n, P{pred}, count_dev);
+}
+
+// ------------------------------------------------------------ reduce_by_key
+// reduce_by_key.hpp:586 with any key comparator and any associative func
+// (it needs no identity and need not commute): the library's kernel
+// (reduce_by_key_kernel.hpp), instantiated for the callables.
+template <typename KT, typename Comp>
+struct as_key_equal {
+    Comp comp;
+    __device__ __forceinline__ bool operator()(KT const& a, KT const& b) const { return static_cast<bool>(comp(a, b)); }
+};
+template <typename V, typename Func>
+struct as_value_op {
+    Func func;
+    __device__ __forceinline__ V operator()(V const& a, V const& b) const { return static_cast<V>(func(a, b)); }
+};
+
+template <typename KT, typename V, typename Eq, typename F, typename CT>
+void reduce_by_key_launch(compute::hip::target const& t, KT const* keys, V const* vals, KT* keys_out, V* vals_out,
+                          uint64_t n, Eq eq, F f, uint64_t* count_dev) {
+    namespace R = K::reduce_by_key_detail;
+    constexpr int E = R::lane_elems<KT, V>();
+    const uint64_t ntiles = R::ntiles_for<KT, V>(n);
+    const std::size_t state = (256 + ntiles * R::state_t<CT, V>::bytes_per_tile() + 255) / 256 * 256;
+    char* ws = static_cast<char*>(scratch(t, state, "reduce_by_key scratch"));
+    compute::hip::detail::check(hpxhip_memset_async(ws, 0, state, t.stream()), "reduce_by_key scratch");
+    R::state_t<CT, V> st{reinterpret_cast<uint64_t*>(ws + 256), error_word(t)};
+    const int vec_ok = reinterpret_cast<uintptr_t>(keys) % (E * sizeof(KT)) == 0 &&
+                       reinterpret_cast<uintptr_t>(vals) % (E * sizeof(V)) == 0;
+    hipLaunchKernelGGL((R::k_reduce_by_key<KT, V, Eq, F, CT>), dim3(static_cast<unsigned>(ntiles)), dim3(R::kThreads),
+                       0, stream_of(t), keys, vals, keys_out, vals_out, n, eq, f, count_dev, st, vec_ok);
+    launched("reduce_by_key (device closure)");
+}
+
+template <typename KT, typename V, typename Comp, typename Func>
+void reduce_by_key(compute::hip::target const& t, KT const* keys, V const* vals, KT* keys_out, V* vals_out,
+                   uint64_t n, Comp const& comp, Func const& func, uint64_t* count_dev) {
+    static_assert((sizeof(KT) == 4 || sizeof(KT) == 8) && (sizeof(V) == 4 || sizeof(V) == 8),
+                  "reduce_by_key (device closure): 4- or 8-byte key and value types");
+    if (n == 0) {
+        compute::hip::detail::check(hpxhip_memset_async(count_dev, 0, sizeof(uint64_t), t.stream()),
+                                    "reduce_by_key count");
+        return;
+    }
+    using Eq = as_key_equal<KT, std::decay_t<Comp>>;
+    constexpr bool builtin = tr::is_binop<Func>;
+    using F = std::conditional_t<builtin, typename scan_op<Func>::type, as_value_op<V, std::decay_t<Func>>>;
+    const F f = [&] {
+        if constexpr (builtin) return F{};
+        else return F{func};
+    }();
+    if (n < (uint64_t{1} << 32))
+        reduce_by_key_launch<KT, V, Eq, F, uint32_t>(t, keys, vals, keys_out, vals_out, n, Eq{comp}, f, count_dev);
+    else
+        reduce_by_key_launch<KT, V, Eq, F, uint64_t>(t, keys, vals, keys_out, vals_out, n, Eq{comp}, f, count_dev);
 }
 
 // --------------------------------------------------------------------- sort

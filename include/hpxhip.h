@@ -130,7 +130,8 @@ enum hpxhip_algo {
     HPXHIP_ALGO_SORT = 3,
     HPXHIP_ALGO_SORT_BY_KEY = 4,
     HPXHIP_ALGO_MERGE = 5,  /* n = n1 + n2 */
-    HPXHIP_ALGO_MERGE_RUNS = 6  /* n = the runs' total (hpxhip_merge_runs, up to 8 runs) */
+    HPXHIP_ALGO_MERGE_RUNS = 6, /* n = the runs' total (hpxhip_merge_runs, up to 8 runs) */
+    HPXHIP_ALGO_REDUCE_BY_KEY = 7 /* dtype = the key dtype, aux_dtype = the value dtype */
 };
 
 typedef struct hpxhip_stream_opaque* hpxhip_stream; /* == hipStream_t */
@@ -222,8 +223,8 @@ int hpxhip_memcpy_async(void* dst, const void* src, size_t bytes, int kind, hpxh
 int hpxhip_memcpy_peer_async(void* dst, int dst_device, const void* src, int src_device,
                              size_t bytes, hpxhip_stream stream);
 int hpxhip_memset_async(void* dst, int value, size_t bytes, hpxhip_stream stream);
-/* Bytes of scratch `algo` needs for n elements of dtype (sort_by_key: the
-   value dtype is passed in `aux_dtype`, else ignored). */
+/* Bytes of scratch `algo` needs for n elements of dtype (sort_by_key and
+   reduce_by_key: the value dtype is passed in `aux_dtype`, else ignored). */
 int hpxhip_scratch_bytes(int algo, int dtype, int aux_dtype, uint64_t n, size_t* bytes);
 
 /* The per-stream scratch cache itself (>= bytes of device memory, reused by
@@ -338,6 +339,31 @@ int hpxhip_scan(int dtype, int op, int inclusive, int conv_kind, const void* con
 int hpxhip_copy_if(int dtype, int pred_kind, const void* pred_arg, const void* in, void* out,
                    uint64_t n, uint64_t* count_dev, hpxhip_stream stream, void* scratch,
                    size_t scratch_bytes);
+
+/* ------------------------------------------------------ reduce_by_key */
+/* reduce_by_key.hpp:586: a run is a maximal range of consecutive equal keys
+   (std::equal_to: integers bitwise; floats by value, so -0.0 == +0.0 is one
+   run and every NaN a run of its own).  Run j gives keys_out[j] = its first
+   key and values_out[j] = its values folded left to right with `op`;
+   *count_dev (uint64, device) receives the number of runs, so the returned
+   iterators are keys_out + count and values_out + count.  One pass: the
+   reference's key-state pass (:294-334), tuple scan (:360-390) and zipped
+   copy_if (:399-411) fused over a segmented decoupled look-back; FP results
+   are bitwise reproducible.  keys_out may be keys_in and values_out may be
+   values_in (exactly aliased, as the reference's own test runs it,
+   tests/unit/parallel/algorithms/reduce_by_key.cpp:162-168); partial overlap
+   is not supported.  BIT_* ops need integer values (else UNSUPPORTED).
+   Two deliberate differences from the reference:
+   - n <= 1: the reference returns the un-advanced output iterators (and at
+     n == 0 dereferences empty ranges, :604-609, FIXME at :302); here
+     *count_dev = n, i.e. the ends of what was written (n == 0 writes nothing
+     else).
+   - only `count` elements of values_out are written; the reference scans
+     into values_out over all n positions first, so its callers size it for n. */
+int hpxhip_reduce_by_key(int key_dtype, int value_dtype, int op, const void* keys_in,
+                         const void* values_in, void* keys_out, void* values_out, uint64_t n,
+                         uint64_t* count_dev, hpxhip_stream stream, void* scratch,
+                         size_t scratch_bytes);
 
 /* --------------------------------------------------------------- sort */
 /* sort.hpp:364: ascending (std::less) or descending (std::greater) sort of

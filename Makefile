@@ -40,6 +40,10 @@ $(BUILD)/csrc/%.o: hpx_amd/csrc/%.hip $(KHDR)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# partition.hip (partition_copy, stable_partition, remove) is part of
+# copy_if.hip's translation unit: one offload bundle for both compactions
+$(BUILD)/csrc/copy_if.o: hpx_amd/csrc/partition.hip
+
 $(LIB): $(KOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KOBJ)
 
@@ -88,7 +92,7 @@ tests/cxx/bin/oracle_sanitize: tests/cxx/oracle_sanitize.cpp oracle/oracle.cpp o
 
 # ... and the hipcc-compiled ones (device closures, HPX_HOST_DEVICE lambdas)
 HIPT     := device_closures partitioned_vector closure_algorithms closure_timing dataflow_stencil bench_targets \
-            reduce_by_key
+            reduce_by_key partition
 HIPTBIN  := $(HIPT:%=tests/cxx/bin/%)
 HTFLAGS  := -O2 -std=c++17 --offload-arch=$(ARCH) --offload-compress -Wall -Wno-unused-parameter -Iinclude
 

@@ -19,6 +19,10 @@ calls one whole-algorithm entry point of the C ABI (include/hpxhip.h):
   sort / sort_by_key         sort.hpp:364, sort_by_key.hpp:42-78
   reduce_by_key              reduce_by_key.hpp:586 (one pass instead of the
                              reference's three, :294-411)
+  partition_copy             partition.hpp:1350
+  stable_partition/partition partition.hpp:292, 1063
+  remove_copy(_if)           remove_copy.hpp:173, 350
+  remove(_if)                remove.hpp:290, 367
   generate (splitmix/iota)   generate.hpp (device generator functors)
   for_loop / for_loop_n      for_loop.hpp:808; for_loop_strided 604,
   for_loop_n_strided         1014 (inductions: for_loop_induction.hpp;
@@ -234,6 +238,95 @@ def copy_if(pol, first, last, dest, pred):
            _vp(dev), stream, None, 0)
     L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8, L.D2H, stream)
     return _finish(is_task, stream, tgt, lambda: (last, dest + _read_host(host, L.U64)))
+
+
+# ------------------------------------------- partition and remove families
+def _partition_call(what, pol, first, last, dest_true, dest_false, pred):
+    """One hpxhip_partition_copy call -> (stream, tgt, is_task, n, count thunk);
+    dest_true / dest_false: an iterator or None (that side is dropped)."""
+    _exec_of(pol)
+    pred = F.require(pred, F.Predicate, what)
+    n = _check_range(first, last)
+    dests = [d for d in (dest_true, dest_false) if d is not None]
+    for d in dests:
+        if not isinstance(d, iterator):
+            raise TypeError(f"{what}: expected device iterators (hpx_amd.compute.iterator)")
+        if d.dtype != first.dtype:
+            raise TypeError(f"{what}: source and destination dtypes differ")
+    if len(dests) == 2 and dest_true.address == dest_false.address:
+        raise ValueError(f"{what}: the two destinations must not be the same range")
+    stream, tgt, is_task = _context(pol, first, *dests)
+    dev, host = _slots_for(tgt).next()
+    arg = L.scalar_buf(first.dtype, pred.arg)
+    L.call("hpxhip_partition_copy", first.dtype, pred.kind, arg, _vp(first.address),
+           _vp(dest_true.address) if dest_true is not None else None,
+           _vp(dest_false.address) if dest_false is not None else None, n, _vp(dev), stream, None, 0)
+    L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8, L.D2H, stream)
+    return stream, tgt, is_task, n, lambda: _read_host(host, L.U64)
+
+
+def partition_copy(pol, first, last, dest_true, dest_false, pred):
+    """partition.hpp:1350: the elements that satisfy pred go to dest_true, the
+    others to dest_false, both in input order (one pass); returns
+    (last, dest_true_end, dest_false_end).  Either destination may be first
+    (exactly aliased), not both."""
+    for d in (dest_true, dest_false):
+        if not isinstance(d, iterator):
+            F.require(pred, F.Predicate, "partition_copy")
+            raise TypeError("partition_copy: expected device iterators (hpx_amd.compute.iterator)")
+    stream, tgt, is_task, n, count = _partition_call("partition_copy", pol, first, last, dest_true, dest_false, pred)
+
+    def ends():
+        c = count()
+        return last, dest_true + c, dest_false + (n - c)
+    return _finish(is_task, stream, tgt, ends)
+
+
+def stable_partition(pol, first, last, pred):
+    """partition.hpp:292: the elements that satisfy pred first, then the
+    others, both in input order; returns first + count."""
+    _exec_of(pol)
+    pred = F.require(pred, F.Predicate, "stable_partition")
+    n = _check_range(first, last)
+    stream, tgt, is_task = _context(pol, first)
+    dev, host = _slots_for(tgt).next()
+    arg = L.scalar_buf(first.dtype, pred.arg)
+    L.call("hpxhip_stable_partition", first.dtype, pred.kind, arg, _vp(first.address), n, _vp(dev), stream, None, 0)
+    L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8, L.D2H, stream)
+    return _finish(is_task, stream, tgt, lambda: first + _read_host(host, L.U64))
+
+
+def partition(pol, first, last, pred):
+    """partition.hpp:1063: any valid partition is allowed; this is the stable one."""
+    return stable_partition(pol, first, last, pred)
+
+
+def remove_copy_if(pol, first, last, dest, pred):
+    """remove_copy.hpp:350: the elements that do NOT satisfy pred, in input
+    order; returns (last, dest_end).  dest may be first."""
+    if not isinstance(dest, iterator):
+        F.require(pred, F.Predicate, "remove_copy_if")
+        raise TypeError("remove_copy_if: expected device iterators (hpx_amd.compute.iterator)")
+    stream, tgt, is_task, n, count = _partition_call("remove_copy_if", pol, first, last, None, dest, pred)
+    return _finish(is_task, stream, tgt, lambda: (last, dest + (n - count())))
+
+
+def remove_copy(pol, first, last, dest, value):
+    """remove_copy.hpp:173: the elements x with !(x == value): a NaN is never
+    removed, 0.0 removes -0.0 too."""
+    return remove_copy_if(pol, first, last, dest, F.equal_to(value))
+
+
+def remove_if(pol, first, last, pred):
+    """remove.hpp:367: remove_copy_if in place; returns first + kept.  The
+    elements from the new end onward keep their old values."""
+    stream, tgt, is_task, n, count = _partition_call("remove_if", pol, first, last, None, first, pred)
+    return _finish(is_task, stream, tgt, lambda: first + (n - count()))
+
+
+def remove(pol, first, last, value):
+    """remove.hpp:290: remove_copy in place."""
+    return remove_if(pol, first, last, F.equal_to(value))
 
 
 # --------------------------------------------------------------- transform
@@ -735,7 +828,8 @@ def _guarded(fn):
     return run
 
 
-for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "copy_n", "copy_if", "transform",
+for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "copy_n", "copy_if", "partition_copy",
+              "stable_partition", "partition", "remove_copy_if", "remove_copy", "remove_if", "remove", "transform",
               "reduce", "transform_reduce", "inclusive_scan", "exclusive_scan", "transform_inclusive_scan",
               "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge", "for_loop_n", "for_loop",
               "for_loop_n_strided", "for_loop_strided"):

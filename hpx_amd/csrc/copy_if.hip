@@ -163,3 +163,7 @@ extern "C" int hpxhip_copy_if(int dtype, int pred_kind, const void* pred_arg, co
         });
     });
 }
+
+// partition_copy, stable_partition and the remove family: the two-sided
+// compaction, in this object (see the head of the file).
+#include "partition.hip"

@@ -529,6 +529,8 @@ int hpxhip_scratch_bytes(int algo, int dtype, int aux_dtype, uint64_t n, size_t*
             if (dtype_size(aux_dtype) == 0) return HPXHIP_ERROR_INVALID_ARGUMENT;
             *bytes = reduce_by_key_scratch_bytes(dtype, aux_dtype, n);
             return 0;
+        case HPXHIP_ALGO_PARTITION_COPY: *bytes = partition_scratch_bytes(dtype, n, false); return 0;
+        case HPXHIP_ALGO_STABLE_PARTITION: *bytes = partition_scratch_bytes(dtype, n, true); return 0;
         default: return HPXHIP_ERROR_INVALID_ARGUMENT;
     }
 }

@@ -18,6 +18,10 @@
 //   sort                         sort.hpp:364                 -> RandomIt
 //   sort_by_key                  sort_by_key.hpp:125          -> tagged_pair<keys, values>
 //   reduce_by_key                reduce_by_key.hpp:586        -> pair<keys_out, values_out>
+//   partition_copy               partition.hpp:1350           -> tagged_tuple<in, out1, out2>
+//   stable_partition, partition  partition.hpp:292, 1063      -> Iter
+//   remove_copy, remove_copy_if  remove_copy.hpp:173, 350     -> tagged_pair<in, out>
+//   remove, remove_if            remove.hpp:290, 367          -> Iter
 //
 // Synchronous policies (seq, par, par_unseq) return the value after the
 // target's stream is synchronised (the reference's bulk_sync_execute,
@@ -403,6 +407,151 @@ detail::result_t<P, util::tagged_pair<In, Out>> copy_if(P&& p, In first, In last
         std::memcpy(&c, b, 8);
         return R{last, dest + static_cast<std::ptrdiff_t>(c)};
     });
+}
+
+// ------------------------------------------- partition and remove families
+// One single-pass, stable, two-sided compaction
+// (hpxhip/kernels/partition_kernel.hpp): the elements that satisfy the
+// predicate to one output, the others (`!pred(x)`) to the other, each in
+// input order.  A destination may be the input range itself (exactly aliased,
+// not both); in place only [first, returned end) is written.  Mapped
+// predicates (traits::pred) run the library's kernels; any other
+// HPX_HOST_DEVICE predicate runs the same kernel as a device closure (hipcc).
+// ot / of: a null pointer drops that side.
+template <typename T, typename Tgt, typename F>
+void partition_dispatch(char const* what, Tgt const& t, T const* in, T* ot, T* of, uint64_t n, F const& f,
+                        uint64_t* count_dev) {
+    if constexpr (detail::is_complete_pred<F>) {
+        using Tr = detail::tr::pred_t<F>;
+        T arg = static_cast<T>(Tr::arg(f));
+        detail::check(hpxhip_partition_copy(detail::dt<T>, Tr::kind, &arg, in, ot, of, n, count_dev, t.stream(),
+                                            nullptr, 0),
+                      what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        if ((!ot && !of) || ot == of) throw hpx::exception(HPXHIP_ERROR_INVALID_ARGUMENT, what);
+        detail::dev::partition_copy(t, in, ot, of, n, f, count_dev);
+#else
+        detail::no_device_mapping<F>(what);
+#endif
+    }
+}
+
+// partition.hpp:1350 -> tagged_tuple<in, out1, out2>
+template <typename P, typename In, typename Out1, typename Out2, typename F>
+detail::result_t<P, util::tagged_tuple<In, Out1, Out2>> partition_copy(P&& p, In first, In last, Out1 dest_true,
+                                                                       Out2 dest_false, F&& f) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out1> && detail::is_dev<Out2>,
+                  "partition_copy: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out1>>::value && std::is_same<T, detail::value_t<Out2>>::value,
+                  "partition_copy: the outputs hold the input's value type");
+    using R = util::tagged_tuple<In, Out1, Out2>;
+    auto const& t = detail::target_of(p, first);
+    uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    partition_dispatch<T>("partition_copy", t, static_cast<T const*>(first.device_ptr()),
+                          static_cast<T*>(dest_true.device_ptr()), static_cast<T*>(dest_false.device_ptr()), n, f,
+                          static_cast<uint64_t*>(slot.device()));
+    detail::fetch_slot(t, slot, 8, "partition_copy count");
+    return detail::finish_slot<R>(p, t, std::move(slot), [last, dest_true, dest_false, n](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return R{last, dest_true + static_cast<std::ptrdiff_t>(c), dest_false + static_cast<std::ptrdiff_t>(n - c)};
+    });
+}
+
+// partition.hpp:292 -> first + (number of elements that satisfy f).  The
+// accepted elements are compacted in place, the rejected ones go to scratch
+// (n elements) and a second kernel copies them behind (hpxhip.h).
+template <typename P, typename It, typename F>
+detail::result_t<P, It> stable_partition(P&& p, It first, It last, F&& f) {
+    static_assert(detail::is_dev<It>, "stable_partition: device iterators required");
+    using T = detail::value_t<It>;
+    auto const& t = detail::target_of(p, first);
+    uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    if constexpr (detail::is_complete_pred<F>) {
+        using Tr = detail::tr::pred_t<F>;
+        T arg = static_cast<T>(Tr::arg(f));
+        detail::check(hpxhip_stable_partition(detail::dt<T>, Tr::kind, &arg, first.device_ptr(), n,
+                                              static_cast<uint64_t*>(slot.device()), t.stream(), nullptr, 0),
+                      "stable_partition");
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::stable_partition(t, static_cast<T*>(first.device_ptr()), n, f,
+                                      static_cast<uint64_t*>(slot.device()));
+#else
+        detail::no_device_mapping<F>("stable_partition");
+#endif
+    }
+    detail::fetch_slot(t, slot, 8, "stable_partition count");
+    return detail::finish_slot<It>(p, t, std::move(slot), [first](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return first + static_cast<std::ptrdiff_t>(c);
+    });
+}
+
+// partition.hpp:1063: any valid partition is allowed; this is the stable one.
+template <typename P, typename It, typename F>
+detail::result_t<P, It> partition(P&& p, It first, It last, F&& f) {
+    return stable_partition(std::forward<P>(p), first, last, std::forward<F>(f));
+}
+
+// remove_copy.hpp:350 -> tagged_pair<in, out>: the elements that do not
+// satisfy f.  dest may be first.
+template <typename P, typename In, typename Out, typename F>
+detail::result_t<P, util::tagged_pair<In, Out>> remove_copy_if(P&& p, In first, In last, Out dest, F&& f) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out>, "remove_copy_if: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out>>::value, "remove_copy_if: the output holds the input's value type");
+    using R = util::tagged_pair<In, Out>;
+    auto const& t = detail::target_of(p, first);
+    uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    partition_dispatch<T>("remove_copy_if", t, static_cast<T const*>(first.device_ptr()), static_cast<T*>(nullptr),
+                          static_cast<T*>(dest.device_ptr()), n, f, static_cast<uint64_t*>(slot.device()));
+    detail::fetch_slot(t, slot, 8, "remove_copy_if count");
+    return detail::finish_slot<R>(p, t, std::move(slot), [last, dest, n](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return R{last, dest + static_cast<std::ptrdiff_t>(n - c)};
+    });
+}
+
+// remove_copy.hpp:173: the elements x with !(x == value) (HPXHIP_P_EQ): a
+// NaN is never removed, 0.0 removes -0.0 too.
+template <typename P, typename In, typename Out, typename V>
+detail::result_t<P, util::tagged_pair<In, Out>> remove_copy(P&& p, In first, In last, Out dest, V const& value) {
+    using T = detail::value_t<In>;
+    return remove_copy_if(std::forward<P>(p), first, last, dest,
+                          compute::hip::functional::equal_to<T>{static_cast<T>(value)});
+}
+
+// remove.hpp:367 / :290: remove_copy_if / remove_copy in place -> the new end;
+// the elements from there onward keep their values.
+template <typename P, typename It, typename F>
+detail::result_t<P, It> remove_if(P&& p, It first, It last, F&& f) {
+    static_assert(detail::is_dev<It>, "remove_if: device iterators required");
+    using T = detail::value_t<It>;
+    auto const& t = detail::target_of(p, first);
+    uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    partition_dispatch<T>("remove_if", t, static_cast<T const*>(first.device_ptr()), static_cast<T*>(nullptr),
+                          static_cast<T*>(first.device_ptr()), n, f, static_cast<uint64_t*>(slot.device()));
+    detail::fetch_slot(t, slot, 8, "remove_if count");
+    return detail::finish_slot<It>(p, t, std::move(slot), [first, n](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return first + static_cast<std::ptrdiff_t>(n - c);
+    });
+}
+
+template <typename P, typename It, typename V>
+detail::result_t<P, It> remove(P&& p, It first, It last, V const& value) {
+    using T = detail::value_t<It>;
+    return remove_if(std::forward<P>(p), first, last, compute::hip::functional::equal_to<T>{static_cast<T>(value)});
 }
 
 // ------------------------------------------------------------- transform
@@ -1227,6 +1376,13 @@ HPXHIP_GUARDED_ALGORITHM(fill_n)
 HPXHIP_GUARDED_ALGORITHM(copy)
 HPXHIP_GUARDED_ALGORITHM(copy_n)
 HPXHIP_GUARDED_ALGORITHM(copy_if)
+HPXHIP_GUARDED_ALGORITHM(partition_copy)
+HPXHIP_GUARDED_ALGORITHM(stable_partition)
+HPXHIP_GUARDED_ALGORITHM(partition)
+HPXHIP_GUARDED_ALGORITHM(remove_copy_if)
+HPXHIP_GUARDED_ALGORITHM(remove_copy)
+HPXHIP_GUARDED_ALGORITHM(remove_if)
+HPXHIP_GUARDED_ALGORITHM(remove)
 HPXHIP_GUARDED_ALGORITHM(transform)
 HPXHIP_GUARDED_ALGORITHM(reduce)
 HPXHIP_GUARDED_ALGORITHM(transform_reduce)
@@ -1275,6 +1431,13 @@ using parallel::v1::merge;
 using parallel::v1::inclusive_scan;
 using parallel::v1::reduce;
 using parallel::v1::reduce_by_key;
+using parallel::v1::partition;
+using parallel::v1::partition_copy;
+using parallel::v1::remove;
+using parallel::v1::remove_copy;
+using parallel::v1::remove_copy_if;
+using parallel::v1::remove_if;
+using parallel::v1::stable_partition;
 using parallel::v1::is_sorted;
 using parallel::v1::sort;
 using parallel::v1::sort_by_key;

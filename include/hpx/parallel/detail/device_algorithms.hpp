@@ -15,6 +15,8 @@
 //                                                   look-back, 16-B tiles)
 //   copy_if                    copy_if_kernel.hpp  (ballot ranks, look-back)
 //   reduce_by_key              reduce_by_key_kernel.hpp (segmented look-back)
+//   partition_copy, stable_partition, remove_copy_if, remove_if
+//                              partition_kernel.hpp (two-sided compaction)
 //   sort (comp, proj)          merge_kernel.hpp    (block sort in LDS, then
 //                                                   merge-path passes)
 //
@@ -43,6 +45,7 @@
 #if HPX_HAVE_HIP_DEVICE_CLOSURES
 #include <hpxhip/kernels/copy_if_kernel.hpp>
 #include <hpxhip/kernels/merge_kernel.hpp>
+#include <hpxhip/kernels/partition_kernel.hpp>
 #include <hpxhip/kernels/reduce_by_key_kernel.hpp>
 #include <hpxhip/kernels/reduce_kernel.hpp>
 #include <hpxhip/kernels/scan_kernel.hpp>
@@ -279,6 +282,86 @@ void copy_if(compute::hip::target const& t, T const* in, T* out, uint64_t n, Pre
     else if (aligned) copy_if_launch<T, P, true, uint64_t>(t, in, out, n, P{pred}, count_dev);
     else if (small) copy_if_launch<T, P, false, uint32_t>(t, in, out, n, P{pred}, count_dev);
     else copy_if_launch<T, P, false, uint64_t>(t, in, out, n, P{pred}, count_dev);
+}
+
+// ------------------------------------------- partition and remove families
+// partition.hpp:1350 / remove_copy.hpp:350 with any predicate: the library's
+// two-sided compaction kernel (partition_kernel.hpp), instantiated for the
+// callable.  Either output may be null or the input itself.  A misaligned
+// input takes the element-wise form.  ws: state_bytes of scratch.
+template <typename T, typename P, bool ALIGNED, typename SV>
+void partition_launch(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n, P p,
+                      uint64_t* count_dev, char* ws) {
+    namespace C = K::partition_detail;
+    const uint64_t ntiles = C::ntiles_for<T>(n);
+    compute::hip::detail::check(
+        hpxhip_memset_async(ws, 0, 256 + ntiles * K::tile_state<SV>::bytes_per_tile(), t.stream()),
+        "partition scratch");
+    K::tile_state<SV> st{reinterpret_cast<uint64_t*>(ws + 256), error_word(t)};
+    // one persistent workgroup per CU (partition.hip)
+    static std::atomic<int> cus[64];
+    const int dev = t.device();
+    int c = dev >= 0 && dev < 64 ? cus[dev].load(std::memory_order_relaxed) : 0;
+    if (c <= 0) {
+        c = static_cast<int>(t.native_handle().processing_units());
+        if (dev >= 0 && dev < 64) cus[dev].store(c, std::memory_order_relaxed);
+    }
+    const uint64_t grid = std::min<uint64_t>(ntiles, static_cast<uint64_t>(c));
+    hipLaunchKernelGGL((C::k_partition<T, P, ALIGNED, SV>), dim3(static_cast<unsigned>(grid)), dim3(C::kThreads), 0,
+                       stream_of(t), in, out_true, out_false, n, uint64_t{0}, p, count_dev,
+                       reinterpret_cast<uint32_t*>(ws), st, ntiles, static_cast<const uint64_t*>(nullptr));
+    launched("partition (device closure)");
+}
+
+template <typename T>
+std::size_t partition_state_bytes(uint64_t n) {
+    return (256 + K::partition_detail::ntiles_for<T>(n) * K::tile_state<uint64_t>::bytes_per_tile() + 255) / 256 * 256;
+}
+
+template <typename T, typename Pred>
+void partition_copy_ws(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n,
+                       Pred const& pred, uint64_t* count_dev, char* ws) {
+    using P = as_bool_pred<T, std::decay_t<Pred>>;
+    const bool aligned = reinterpret_cast<uintptr_t>(in) % 16 == 0;
+    const bool small = n < (uint64_t{1} << 32);
+    if (aligned && small) partition_launch<T, P, true, uint32_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
+    else if (aligned) partition_launch<T, P, true, uint64_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
+    else if (small) partition_launch<T, P, false, uint32_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
+    else partition_launch<T, P, false, uint64_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
+}
+
+template <typename T, typename Pred>
+void partition_copy(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n,
+                    Pred const& pred, uint64_t* count_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "partition (device closure): 4- or 8-byte element types");
+    if (n == 0) {
+        compute::hip::detail::check(hpxhip_memset_async(count_dev, 0, sizeof(uint64_t), t.stream()), "partition count");
+        return;
+    }
+    char* ws = static_cast<char*>(scratch(t, partition_state_bytes<T>(n), "partition scratch"));
+    partition_copy_ws(t, in, out_true, out_false, n, pred, count_dev, ws);
+}
+
+// partition.hpp:292: accepted elements compacted in place, rejected ones to
+// scratch, k_partition_tail copies them to [count, n) (count read on the
+// device).
+template <typename T, typename Pred>
+void stable_partition(compute::hip::target const& t, T* data, uint64_t n, Pred const& pred, uint64_t* count_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "partition (device closure): 4- or 8-byte element types");
+    namespace C = K::partition_detail;
+    if (n == 0) {
+        compute::hip::detail::check(hpxhip_memset_async(count_dev, 0, sizeof(uint64_t), t.stream()), "partition count");
+        return;
+    }
+    const std::size_t state = partition_state_bytes<T>(n);
+    char* ws = static_cast<char*>(scratch(t, state + n * sizeof(T), "stable_partition scratch"));
+    T* rejected = reinterpret_cast<T*>(ws + state);
+    partition_copy_ws(t, static_cast<T const*>(data), data, rejected, n, pred, count_dev, ws);
+    const uint64_t nvec = n / (16 / sizeof(T)) + 1;
+    const uint64_t blocks = std::min<uint64_t>((nvec + C::kTailThreads - 1) / C::kTailThreads, 2048);
+    hipLaunchKernelGGL((C::k_partition_tail<T>), dim3(static_cast<unsigned>(blocks)), dim3(C::kTailThreads), 0,
+                       stream_of(t), static_cast<T const*>(rejected), data, n, static_cast<const uint64_t*>(count_dev));
+    launched("stable_partition (device closure)");
 }
 
 // ------------------------------------------------------------ reduce_by_key

@@ -144,7 +144,7 @@ struct algorithm_result {
 }}  // namespace util::detail
 
 // hpx::util::tagged_pair / tagged_tuple results of copy, transform, copy_if,
-// sort_by_key (hpx/util/tagged_pair.hpp); accessors named by the tags.
+// partition_copy, remove_copy, sort_by_key (hpx/util/tagged_pair.hpp); accessors named by the tags.
 namespace util {
 // hpx/parallel/util/projection_identity.hpp: the default projection of the
 // algorithms that take one (sort.hpp:364).
@@ -172,6 +172,10 @@ struct tagged_tuple {
     A in1() const { return first; }
     B in2() const { return second; }
     C out() const { return third; }
+    // tagged_tuple<in, out1, out2> of partition_copy (partition.hpp:1350)
+    A in() const { return first; }
+    B out1() const { return second; }
+    C out2() const { return third; }
 };
 }  // namespace util
 }}  // namespace hpx::parallel

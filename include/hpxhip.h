@@ -131,7 +131,9 @@ enum hpxhip_algo {
     HPXHIP_ALGO_SORT_BY_KEY = 4,
     HPXHIP_ALGO_MERGE = 5,  /* n = n1 + n2 */
     HPXHIP_ALGO_MERGE_RUNS = 6, /* n = the runs' total (hpxhip_merge_runs, up to 8 runs) */
-    HPXHIP_ALGO_REDUCE_BY_KEY = 7 /* dtype = the key dtype, aux_dtype = the value dtype */
+    HPXHIP_ALGO_REDUCE_BY_KEY = 7, /* dtype = the key dtype, aux_dtype = the value dtype */
+    HPXHIP_ALGO_PARTITION_COPY = 8,
+    HPXHIP_ALGO_STABLE_PARTITION = 9 /* the tile state plus n elements */
 };
 
 typedef struct hpxhip_stream_opaque* hpxhip_stream; /* == hipStream_t */
@@ -339,6 +341,34 @@ int hpxhip_scan(int dtype, int op, int inclusive, int conv_kind, const void* con
 int hpxhip_copy_if(int dtype, int pred_kind, const void* pred_arg, const void* in, void* out,
                    uint64_t n, uint64_t* count_dev, hpxhip_stream stream, void* scratch,
                    size_t scratch_bytes);
+
+/* ---------------------------------------- partition / remove family */
+/* partition.hpp:292,1063,1350, remove_copy.hpp:173,350, remove.hpp:290,367:
+   one single-pass, stable, two-sided compaction.  The elements that satisfy
+   the predicate go to out_true, the others (`!pred(x)`: a NaN under P_LT is
+   rejected) to out_false, each side in input order; *count_dev (uint64,
+   device) receives the number of accepted elements, the rejected count is
+   n - *count_dev.  out_true or out_false may be NULL (that side is dropped;
+   a NULL out_true is remove_copy_if), but not both.  Each output may be
+   exactly `in` (same pointer: out_false == in is remove_if), but not both;
+   the outputs must not overlap each other and partial overlap with `in` is
+   not supported.  In place only [0, count) of the aliased output is written:
+   the elements from the new end onward keep their values.  n == 0 writes
+   *count_dev = 0 and nothing else.  Pointers are aligned to their element
+   size.  INVALID_ARGUMENT: a null count, both outputs null,
+   out_true == out_false (which covers both equal to `in`). */
+int hpxhip_partition_copy(int dtype, int pred_kind, const void* pred_arg, const void* in,
+                          void* out_true, void* out_false, uint64_t n, uint64_t* count_dev,
+                          hpxhip_stream stream, void* scratch, size_t scratch_bytes);
+/* Stable partition of data[0, n) in place: the accepted elements first, then
+   the rejected ones, both in input order; *count_dev receives the accepted
+   count.  The accepted elements are compacted in place, the rejected ones go
+   to scratch, and a second kernel reads the count from device memory and
+   copies them to [count, n) (no host round trip).  Scratch
+   (HPXHIP_ALGO_STABLE_PARTITION): the tile state plus n elements. */
+int hpxhip_stable_partition(int dtype, int pred_kind, const void* pred_arg, void* data, uint64_t n,
+                            uint64_t* count_dev, hpxhip_stream stream, void* scratch,
+                            size_t scratch_bytes);
 
 /* ------------------------------------------------------ reduce_by_key */
 /* reduce_by_key.hpp:586: a run is a maximal range of consecutive equal keys

@@ -14,7 +14,7 @@ BUILD    := build
 HIPFLAGS := -O3 --offload-arch=$(ARCH) -fPIC -std=c++17 -ffp-contract=off --offload-compress \
             -Wall -Wno-unused-result -Wno-unused-function -Iinclude
 LIB      := hpx_amd/libhpxhip.so
-KSRC     := runtime elementwise reduce scan copy_if sort merge stencil
+KSRC     := runtime elementwise reduce scan compaction sort merge stencil
 KOBJ     := $(KSRC:%=$(BUILD)/csrc/%.o)
 KHDR     := $(wildcard hpx_amd/csrc/*.hpp) $(wildcard include/hpxhip/kernels/*.hpp) include/hpxhip.h
 
@@ -39,10 +39,6 @@ oracle: $(ORACLE)
 $(BUILD)/csrc/%.o: hpx_amd/csrc/%.hip $(KHDR)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# partition.hip (partition_copy, stable_partition, remove) is part of
-# copy_if.hip's translation unit: one offload bundle for both compactions
-$(BUILD)/csrc/copy_if.o: hpx_amd/csrc/partition.hip
 
 $(LIB): $(KOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KOBJ)

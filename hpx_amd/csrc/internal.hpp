@@ -280,15 +280,6 @@ struct device_guard {
     }
 };
 
-// Elements needed to bring `p` to a 16-byte boundary (in units of elem_size).
-inline uint64_t head_to_align16(const void* p, size_t elem_size) {
-    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
-    const uintptr_t mis = a & 15u;
-    if (mis == 0) return 0;
-    if (mis % elem_size != 0) return UINT64_MAX;  // never aligns
-    return (16u - mis) / elem_size;
-}
-
 // ------------------------------------------------------------- scratch
 // Per-stream cached device scratch; returns a pointer with at least `bytes`
 // bytes (grown with hipMalloc -- not graph-capturable).

@@ -378,7 +378,7 @@ __global__ __launch_bounds__(kMwThreads, HPXHIP_MW_MINW) void k_mw_merge(const U
     }
     // write-out: a head up to the output's next 128-B line, 16-B vectors, a
     // tail (out 16-B aligned when VEC); line-aligned vectors keep two waves
-    // from writing halves of one line (copy_if_kernel.hpp OUT_ALIGN)
+    // from writing halves of one line (compaction_kernel.hpp store_run)
     U* o = out + pos;
     constexpr int V = 16 / sizeof(U);
     using VT = vec<U, V>;

@@ -411,7 +411,7 @@ detail::result_t<P, util::tagged_pair<In, Out>> copy_if(P&& p, In first, In last
 
 // ------------------------------------------- partition and remove families
 // One single-pass, stable, two-sided compaction
-// (hpxhip/kernels/partition_kernel.hpp): the elements that satisfy the
+// (hpxhip/kernels/compaction_kernel.hpp): the elements that satisfy the
 // predicate to one output, the others (`!pred(x)`) to the other, each in
 // input order.  A destination may be the input range itself (exactly aliased,
 // not both); in place only [first, returned end) is written.  Mapped

@@ -13,10 +13,10 @@
 //                                                   fixed-order partial fold)
 //   scans                      scan_kernel.hpp     (single pass, decoupled
 //                                                   look-back, 16-B tiles)
-//   copy_if                    copy_if_kernel.hpp  (ballot ranks, look-back)
+//   copy_if, partition_copy, stable_partition, remove_copy_if, remove_if
+//                              compaction_kernel.hpp (ballot ranks, look-back;
+//                                                   one- and two-sided)
 //   reduce_by_key              reduce_by_key_kernel.hpp (segmented look-back)
-//   partition_copy, stable_partition, remove_copy_if, remove_if
-//                              partition_kernel.hpp (two-sided compaction)
 //   sort (comp, proj)          merge_kernel.hpp    (block sort in LDS, then
 //                                                   merge-path passes)
 //
@@ -43,9 +43,8 @@
 #include <utility>
 
 #if HPX_HAVE_HIP_DEVICE_CLOSURES
-#include <hpxhip/kernels/copy_if_kernel.hpp>
+#include <hpxhip/kernels/compaction_kernel.hpp>
 #include <hpxhip/kernels/merge_kernel.hpp>
-#include <hpxhip/kernels/partition_kernel.hpp>
 #include <hpxhip/kernels/reduce_by_key_kernel.hpp>
 #include <hpxhip/kernels/reduce_kernel.hpp>
 #include <hpxhip/kernels/scan_kernel.hpp>
@@ -221,84 +220,18 @@ void scan(compute::hip::target const& t, V const* in, V* out, uint64_t n, Op con
     }
 }
 
-// ------------------------------------------------------------------ copy_if
+// ----------------------------------- copy_if, partition and remove families
+// copy.hpp:585, partition.hpp:1350 / remove_copy.hpp:350 with any predicate:
+// the library's compaction kernel through the library's launcher
+// (compaction_kernel.hpp), instantiated for the callable.  A misaligned range
+// takes the head split and the vector kernel, as in the library.
 template <typename T, typename Pred>
 struct as_bool_pred {
     Pred pred;
     __device__ __forceinline__ bool operator()(T x) const { return static_cast<bool>(pred(x)); }
 };
 
-template <typename T, typename P, bool ALIGNED, typename SV>
-void copy_if_launch(compute::hip::target const& t, T const* in, T* out, uint64_t n, P p, uint64_t* count_dev) {
-    namespace C = K::copy_if_detail;
-    constexpr int R = 8;
-    constexpr uint64_t tile = C::tile_elems<T, R>();
-    const uint64_t ntiles = (n + tile - 1) / tile;
-    const std::size_t state = (256 + ntiles * K::tile_state<SV>::bytes_per_tile() + 255) / 256 * 256;
-    char* ws = static_cast<char*>(scratch(t, state, "copy_if scratch"));
-    compute::hip::detail::check(hpxhip_memset_async(ws, 0, state, t.stream()), "copy_if scratch");
-    K::tile_state<SV> st{reinterpret_cast<uint64_t*>(ws + 256), error_word(t)};
-    if constexpr (ALIGNED) {
-        // r05: the shipped pipelined form (copy_if.hip), one persistent
-        // workgroup per CU
-        static std::atomic<int> cus[64];
-        const int dev = t.device();
-        int c = dev >= 0 && dev < 64 ? cus[dev].load(std::memory_order_relaxed) : 0;
-        if (c <= 0) {
-            c = static_cast<int>(t.native_handle().processing_units());
-            if (dev >= 0 && dev < 64) cus[dev].store(c, std::memory_order_relaxed);
-        }
-        const uint64_t grid = std::min<uint64_t>(ntiles, static_cast<uint64_t>(c));
-        hipLaunchKernelGGL((C::k_copy_if_pipe<T, P, R, SV>), dim3(static_cast<unsigned>(grid)), dim3(C::kThreads), 0,
-                           stream_of(t), in, out, n, p, count_dev, reinterpret_cast<uint32_t*>(ws), st, ntiles,
-                           static_cast<const uint64_t*>(nullptr));
-        launched("copy_if (device closure)");
-        return;
-    }
-    // blockIdx tile order with the fixed-association look-back (the shipped
-    // choice for copy_if, copy_if.hip); 4 waves per SIMD: a user predicate
-    // may need more than 64 VGPRs.  r04: the shipped kernel's 8-byte
-    // write-out (nt 16-B stores, 4 rounds per LDS batch) and one-hop
-    // look-back took the lambda copy_if from 1.0x to 1.23x of the kind path
-    // here (profiles/r04_closure_timing_copyif.log), so this form keeps them off.
-    hipLaunchKernelGGL((C::k_copy_if<T, P, ALIGNED, R, 4, 0, SV, false, false, 1, true>),
-                       dim3(static_cast<unsigned>(ntiles)),
-                       dim3(C::kThreads), 0, stream_of(t), in, out, n, p, count_dev, reinterpret_cast<uint32_t*>(ws),
-                       st, ntiles, static_cast<const uint64_t*>(nullptr));
-    launched("copy_if (device closure)");
-}
-
-template <typename T, typename Pred>
-void copy_if(compute::hip::target const& t, T const* in, T* out, uint64_t n, Pred const& pred, uint64_t* count_dev) {
-    static_assert(16 % sizeof(T) == 0, "copy_if (device closure): element size must divide 16 bytes");
-    using P = as_bool_pred<T, std::decay_t<Pred>>;
-    if (n == 0) {
-        compute::hip::detail::check(hpxhip_memset_async(count_dev, 0, sizeof(uint64_t), t.stream()), "copy_if count");
-        return;
-    }
-    const bool aligned = reinterpret_cast<uintptr_t>(in) % 16 == 0;
-    const bool small = n < (uint64_t{1} << 32);
-    if (aligned && small) copy_if_launch<T, P, true, uint32_t>(t, in, out, n, P{pred}, count_dev);
-    else if (aligned) copy_if_launch<T, P, true, uint64_t>(t, in, out, n, P{pred}, count_dev);
-    else if (small) copy_if_launch<T, P, false, uint32_t>(t, in, out, n, P{pred}, count_dev);
-    else copy_if_launch<T, P, false, uint64_t>(t, in, out, n, P{pred}, count_dev);
-}
-
-// ------------------------------------------- partition and remove families
-// partition.hpp:1350 / remove_copy.hpp:350 with any predicate: the library's
-// two-sided compaction kernel (partition_kernel.hpp), instantiated for the
-// callable.  Either output may be null or the input itself.  A misaligned
-// input takes the element-wise form.  ws: state_bytes of scratch.
-template <typename T, typename P, bool ALIGNED, typename SV>
-void partition_launch(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n, P p,
-                      uint64_t* count_dev, char* ws) {
-    namespace C = K::partition_detail;
-    const uint64_t ntiles = C::ntiles_for<T>(n);
-    compute::hip::detail::check(
-        hpxhip_memset_async(ws, 0, 256 + ntiles * K::tile_state<SV>::bytes_per_tile(), t.stream()),
-        "partition scratch");
-    K::tile_state<SV> st{reinterpret_cast<uint64_t*>(ws + 256), error_word(t)};
-    // one persistent workgroup per CU (partition.hip)
+inline int cus_of(compute::hip::target const& t) {
     static std::atomic<int> cus[64];
     const int dev = t.device();
     int c = dev >= 0 && dev < 64 ? cus[dev].load(std::memory_order_relaxed) : 0;
@@ -306,40 +239,33 @@ void partition_launch(compute::hip::target const& t, T const* in, T* out_true, T
         c = static_cast<int>(t.native_handle().processing_units());
         if (dev >= 0 && dev < 64) cus[dev].store(c, std::memory_order_relaxed);
     }
-    const uint64_t grid = std::min<uint64_t>(ntiles, static_cast<uint64_t>(c));
-    hipLaunchKernelGGL((C::k_partition<T, P, ALIGNED, SV>), dim3(static_cast<unsigned>(grid)), dim3(C::kThreads), 0,
-                       stream_of(t), in, out_true, out_false, n, uint64_t{0}, p, count_dev,
-                       reinterpret_cast<uint32_t*>(ws), st, ntiles, static_cast<const uint64_t*>(nullptr));
-    launched("partition (device closure)");
+    return c;
 }
 
-template <typename T>
-std::size_t partition_state_bytes(uint64_t n) {
-    return (256 + K::partition_detail::ntiles_for<T>(n) * K::tile_state<uint64_t>::bytes_per_tile() + 255) / 256 * 256;
+// ws: compaction_detail::state_bytes<T>(n) of scratch
+template <bool TWO_SIDED, typename T, typename Pred>
+void compact(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n, Pred const& pred,
+             uint64_t* count_dev, void* ws, char const* what) {
+    using P = as_bool_pred<T, std::decay_t<Pred>>;
+    const hipError_t e = K::compaction_detail::launch<TWO_SIDED>(in, out_true, out_false, n, P{pred}, count_dev, ws,
+                                                                 error_word(t), cus_of(t), false, stream_of(t));
+    if (e != hipSuccess) throw hpx::kernel_error(static_cast<int>(e), std::string(what) + ": " + hipGetErrorString(e));
 }
 
 template <typename T, typename Pred>
-void partition_copy_ws(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n,
-                       Pred const& pred, uint64_t* count_dev, char* ws) {
-    using P = as_bool_pred<T, std::decay_t<Pred>>;
-    const bool aligned = reinterpret_cast<uintptr_t>(in) % 16 == 0;
-    const bool small = n < (uint64_t{1} << 32);
-    if (aligned && small) partition_launch<T, P, true, uint32_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
-    else if (aligned) partition_launch<T, P, true, uint64_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
-    else if (small) partition_launch<T, P, false, uint32_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
-    else partition_launch<T, P, false, uint64_t>(t, in, out_true, out_false, n, P{pred}, count_dev, ws);
+void copy_if(compute::hip::target const& t, T const* in, T* out, uint64_t n, Pred const& pred, uint64_t* count_dev) {
+    static_assert(16 % sizeof(T) == 0, "copy_if (device closure): element size must divide 16 bytes");
+    void* ws = scratch(t, K::compaction_detail::state_bytes<T>(n), "copy_if scratch");
+    compact<false>(t, in, out, static_cast<T*>(nullptr), n, pred, count_dev, ws, "copy_if (device closure)");
 }
 
+// Either output may be null or the input itself.
 template <typename T, typename Pred>
 void partition_copy(compute::hip::target const& t, T const* in, T* out_true, T* out_false, uint64_t n,
                     Pred const& pred, uint64_t* count_dev) {
     static_assert(sizeof(T) == 4 || sizeof(T) == 8, "partition (device closure): 4- or 8-byte element types");
-    if (n == 0) {
-        compute::hip::detail::check(hpxhip_memset_async(count_dev, 0, sizeof(uint64_t), t.stream()), "partition count");
-        return;
-    }
-    char* ws = static_cast<char*>(scratch(t, partition_state_bytes<T>(n), "partition scratch"));
-    partition_copy_ws(t, in, out_true, out_false, n, pred, count_dev, ws);
+    void* ws = scratch(t, K::compaction_detail::state_bytes<T>(n), "partition scratch");
+    compact<true>(t, in, out_true, out_false, n, pred, count_dev, ws, "partition (device closure)");
 }
 
 // partition.hpp:292: accepted elements compacted in place, rejected ones to
@@ -348,20 +274,14 @@ void partition_copy(compute::hip::target const& t, T const* in, T* out_true, T* 
 template <typename T, typename Pred>
 void stable_partition(compute::hip::target const& t, T* data, uint64_t n, Pred const& pred, uint64_t* count_dev) {
     static_assert(sizeof(T) == 4 || sizeof(T) == 8, "partition (device closure): 4- or 8-byte element types");
-    namespace C = K::partition_detail;
-    if (n == 0) {
-        compute::hip::detail::check(hpxhip_memset_async(count_dev, 0, sizeof(uint64_t), t.stream()), "partition count");
-        return;
-    }
-    const std::size_t state = partition_state_bytes<T>(n);
+    namespace C = K::compaction_detail;
+    const std::size_t state = C::state_bytes<T>(n);
     char* ws = static_cast<char*>(scratch(t, state + n * sizeof(T), "stable_partition scratch"));
     T* rejected = reinterpret_cast<T*>(ws + state);
-    partition_copy_ws(t, static_cast<T const*>(data), data, rejected, n, pred, count_dev, ws);
-    const uint64_t nvec = n / (16 / sizeof(T)) + 1;
-    const uint64_t blocks = std::min<uint64_t>((nvec + C::kTailThreads - 1) / C::kTailThreads, 2048);
-    hipLaunchKernelGGL((C::k_partition_tail<T>), dim3(static_cast<unsigned>(blocks)), dim3(C::kTailThreads), 0,
-                       stream_of(t), static_cast<T const*>(rejected), data, n, static_cast<const uint64_t*>(count_dev));
-    launched("stable_partition (device closure)");
+    compact<true>(t, static_cast<T const*>(data), data, rejected, n, pred, count_dev, ws,
+                  "stable_partition (device closure)");
+    const hipError_t e = C::launch_tail(static_cast<T const*>(rejected), data, n, count_dev, cus_of(t), stream_of(t));
+    if (e != hipSuccess) throw hpx::kernel_error(static_cast<int>(e), "stable_partition (device closure)");
 }
 
 // ------------------------------------------------------------ reduce_by_key

@@ -20,7 +20,7 @@
 #include <type_traits>
 
 // Ablation builds only (-DHPXHIP_TILE_DYN_ID=true): tile ids of the single-
-// pass kernels (scan, copy_if, onesweep sort passes) from an atomic counter
+// pass kernels (scan, onesweep sort passes) from an atomic counter
 // instead of blockIdx (lookback.hpp).
 #ifndef HPXHIP_TILE_DYN_ID
 #define HPXHIP_TILE_DYN_ID false
@@ -152,6 +152,15 @@ template <typename T>
 struct vec_width {
     static constexpr int value = 16 / sizeof(T);
 };
+
+// Elements before the first 16-B boundary of p (UINT64_MAX: p is not
+// element-aligned, so no head makes it 16-B aligned).
+__host__ __device__ inline uint64_t head_to_align16(const void* p, size_t elem_size) {
+    const uintptr_t mis = reinterpret_cast<uintptr_t>(p) & 15u;
+    if (mis == 0) return 0;
+    if (mis % elem_size != 0) return UINT64_MAX;
+    return (16u - mis) / elem_size;
+}
 
 // ---------------------------------------------------------------------------
 // Streaming accesses: `global_load/store ... nt` (nontemporal cache policy).

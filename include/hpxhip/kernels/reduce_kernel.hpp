@@ -136,15 +136,6 @@ __host__ __device__ inline uint64_t max_blocks(uint64_t n) {
     return b ? b : 1;
 }
 
-// Elements before the first 16-B boundary of p (UINT64_MAX: p is not
-// element-aligned, so no head makes it 16-B aligned).
-__host__ __device__ inline uint64_t head_to_align16(const void* p, size_t elem_size) {
-    const uintptr_t mis = reinterpret_cast<uintptr_t>(p) & 15u;
-    if (mis == 0) return 0;
-    if (mis % elem_size != 0) return UINT64_MAX;
-    return (16u - mis) / elem_size;
-}
-
 // Queue the reduction of [a, a + n) (and b for BINARY) into *out on s.
 // partials: max_blocks(n) TA values of scratch.  Returns a hipError_t.
 template <typename TI, typename TA, typename Src, typename Op, bool BINARY>

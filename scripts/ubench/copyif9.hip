@@ -1,12 +1,11 @@
 // Microbenchmark (round 5, copyif9): the pipelined persistent copy_if
-// (k_copy_if_pipe: one workgroup per CU, the tile's hits staged in LDS, the
-// next tile's loads issued before the look-back and write-out) against the
-// shipped one-tile-per-workgroup kernel, int64 at 2^30 and int32 at 2^31,
-// predicate !(x < 0) on ~50 % hits; also ragged n and an output at 8 B mod
-// 16.  Each variant's output is compared element for element with the
-// shipped kernel's.
+// (k_compact, one-sided: one workgroup per CU, the tile's hits staged in LDS,
+// the next tile's loads issued before the look-back and write-out) in other
+// shapes, int64 at 2^30 and int32 at 2^31, predicate !(x < 0) on ~50 % hits;
+// also ragged n and an output at 8 B mod 16.  Each variant's output is
+// compared element for element with the first run's.
 // build: hipcc -O3 --offload-arch=gfx950 -std=c++17 -I../../include -I../../hpx_amd/csrc copyif9.hip -o copyif9
-#include <hpxhip/kernels/copy_if_kernel.hpp>
+#include <hpxhip/kernels/compaction_kernel.hpp>
 #include "internal.hpp"
 #include <algorithm>
 #include <cstdio>
@@ -14,7 +13,7 @@
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("err %s line %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
 using namespace hpxhip;
-using namespace hpxhip::copy_if_detail;
+using namespace hpxhip::compaction_detail;
 
 template <typename T>
 __global__ void k_fill(T* p, uint64_t n) {
@@ -34,9 +33,8 @@ struct harness {
   using P = pred_fn<HPXHIP_P_NOT_LT, T>;
   uint64_t N; T *in, *out, *ref_out; char* ws; uint32_t* err; uint64_t* cnt; unsigned long long* bad;
   hipEvent_t e0, e1; uint64_t ref = 0;
-  // kind 0: r04's k_copy_if; 1: k_copy_if_pipe with 16-B aligned vectors,
-  // `per_cu` workgroups per CU; 2: k_copy_if_pipe with its vectors 128-B
-  // aligned in the output (shipped after lease r5/ab)
+  // kind 1: k_compact with 16-B aligned vectors, `per_cu` workgroups per CU;
+  // 2: k_compact with its vectors 128-B aligned in the output (shipped)
   template <int KIND, int R = 8, int MINW = 4>
   void run(const char* name, int per_cu = 1) {
     using SV = uint32_t;
@@ -45,19 +43,10 @@ struct harness {
     tile_state<SV> st{reinterpret_cast<uint64_t*>(ws + 256), err};
     auto launch = [&] {
       CK(hipMemsetAsync(ws, 0, total, 0));
-      if constexpr (KIND == 0) {
-        constexpr bool W = sizeof(T) == 8;
-        k_copy_if<T, P, true, R, 8, 0, SV, false, W, W ? 4 : 1, true, kThreads, W, W><<<ntiles, kThreads>>>(
-            in, out, N, P{0}, cnt, reinterpret_cast<uint32_t*>(ws), st, ntiles);
-      } else if constexpr (KIND == 1) {
-        const uint64_t g = std::min<uint64_t>(ntiles, (uint64_t)g_cus * per_cu);
-        k_copy_if_pipe<T, P, R, SV, MINW, 16><<<g, kThreads>>>(in, out, N, P{0}, cnt, reinterpret_cast<uint32_t*>(ws),
-                                                               st, ntiles);
-      } else {
-        const uint64_t g = std::min<uint64_t>(ntiles, (uint64_t)g_cus * per_cu);
-        k_copy_if_pipe<T, P, R, SV, MINW, 128><<<g, kThreads>>>(in, out, N, P{0}, cnt, reinterpret_cast<uint32_t*>(ws),
-                                                                st, ntiles);
-      }
+      const uint64_t g = std::min<uint64_t>(ntiles, (uint64_t)g_cus * per_cu);
+      k_compact<T, P, true, SV, false, MINW, R, KIND == 1 ? 16 : 128><<<g, kThreads>>>(
+          in, out, static_cast<T*>(nullptr), N, uint64_t{0}, P{0}, cnt, reinterpret_cast<uint32_t*>(ws), st, ntiles,
+          static_cast<const uint64_t*>(nullptr));
     };
     launch(); CK(hipDeviceSynchronize());
     uint64_t c = 0; CK(hipMemcpy(&c, cnt, 8, hipMemcpyDeviceToHost));
@@ -92,7 +81,6 @@ int main(int argc, char** argv) {
     {
       harness<int64_t> h{1ull << 30, (int64_t*)in, (int64_t*)out, (int64_t*)ref_out, ws, err, cnt, bad, e0, e1};
       k_fill<int64_t><<<((1ull << 30) + 255) / 256, 256>>>(h.in, h.N); CK(hipDeviceSynchronize());
-      h.run<0>("T1024 R8 2/CU (shipped r04)");
       h.run<1>("pipe R8 1/CU");
       h.run<2>("pipe R8 1/CU, 128-B aligned vectors");
       if (!quick) {
@@ -103,19 +91,15 @@ int main(int argc, char** argv) {
     }
     if (!quick) {
       harness<int64_t> h{(1ull << 30) - 3, (int64_t*)in, (int64_t*)out + 1, (int64_t*)ref_out, ws, err, cnt, bad, e0, e1};
-      h.run<0>("n - 3, out 8 B mod 16: shipped");
       h.run<1>("n - 3, out 8 B mod 16: pipe R8");
       h.run<2>("n - 3, out 8 B mod 16: pipe R8 128-B");
       harness<int64_t> hs{100003, (int64_t*)in, (int64_t*)out + 1, (int64_t*)ref_out, ws, err, cnt, bad, e0, e1};
-      hs.run<0>("n 100003: shipped");
       hs.run<1>("n 100003: pipe R8");
       harness<int32_t> h4{1ull << 31, (int32_t*)in, (int32_t*)out, (int32_t*)ref_out, ws, err, cnt, bad, e0, e1};
       k_fill<int32_t><<<((1ull << 31) + 255) / 256, 256>>>(h4.in, h4.N); CK(hipDeviceSynchronize());
-      h4.run<0>("T1024 R8 2/CU (shipped)");
       h4.run<1>("pipe R8 1/CU");
       h4.run<2>("pipe R8 1/CU, 128-B aligned vectors");
       harness<int32_t> h5{(1ull << 31) - 5, (int32_t*)in, (int32_t*)out + 1, (int32_t*)ref_out, ws, err, cnt, bad, e0, e1};
-      h5.run<0>("n - 5, out 4 B mod 16: shipped");
       h5.run<1>("n - 5, out 4 B mod 16: pipe R8");
     }
   }

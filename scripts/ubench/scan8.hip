@@ -17,7 +17,7 @@ namespace hpxhip {
 namespace scan_detail {
 // Pipelined form (r05, measured here and rejected: 3.23-3.38 ms against
 // 2.56 for the shipped k_scan at 2^30, profiles/r05_ubench_scan8_pipe.log): the copy_if
-// structure (copy_if_kernel.hpp k_copy_if_pipe) for the scan.  A persistent
+// structure (compaction_kernel.hpp k_compact) for the scan.  A persistent
 // grid of one 1024-thread workgroup per CU claims 128-KiB tiles in order; a
 // tile's wave-local scan goes to LDS (the whole tile), the next tile's loads
 // are issued into the registers it left, and only then does wave 0 take the

@@ -221,6 +221,60 @@ void test_copy_if(hip::default_executor& exec, std::mt19937_64& gen, std::size_t
     same(gf, ef, "copy_if f32", n);
 }
 
+// Lambda predicates on begin() + 1: the device-closure layer splits the head
+// off a misaligned range and runs the vector kernel on the rest.
+template <typename T>
+void test_compaction_misaligned(hip::default_executor& exec, std::mt19937_64& gen, std::size_t n) {
+    auto pol = ex::par.on(exec);
+    std::vector<T> h(n);
+    for (auto& x : h) x = T(gen() % 1000003);
+    auto pred = [] HPX_HOST_DEVICE(T x) { return x % 3 == 1; };
+    const T canary = T(-7);
+    const std::vector<T> blank(n, canary);
+    std::vector<T> acc, rej;
+    std::partition_copy(h.begin() + 1, h.end(), std::back_inserter(acc), std::back_inserter(rej), pred);
+    auto prefix = [](std::vector<T> v, std::size_t cnt) {
+        v.resize(cnt);
+        return v;
+    };
+    {
+        std::vector<T> e;
+        std::copy_if(h.begin() + 1, h.end(), std::back_inserter(e), pred);
+        auto d = to_dev(h, exec.target()), o = to_dev(blank, exec.target());
+        auto r = hpx::parallel::copy_if(pol, d.begin() + 1, d.end(), o.begin(), pred);
+        HPX_TEST(r.in() == d.end());
+        const std::size_t cnt = static_cast<std::size_t>(r.out() - o.begin());
+        auto got = to_host(o);
+        HPX_TEST(cnt < n && got[cnt] == canary);
+        same(prefix(got, cnt), e, "copy_if (begin + 1, lambda)", n);
+    }
+    {
+        auto d = to_dev(h, exec.target()), ot = to_dev(blank, exec.target()), of = to_dev(blank, exec.target());
+        auto r = hpx::parallel::partition_copy(pol, d.begin() + 1, d.end(), ot.begin(), of.begin(), pred);
+        HPX_TEST(r.in() == d.end());
+        same(prefix(to_host(ot), static_cast<std::size_t>(r.out1() - ot.begin())), acc,
+             "partition_copy (begin + 1, lambda): accepted", n);
+        same(prefix(to_host(of), static_cast<std::size_t>(r.out2() - of.begin())), rej,
+             "partition_copy (begin + 1, lambda): rejected", n);
+    }
+    {  // from the new end onward the old values, as std::remove_if leaves integers
+        std::vector<T> e = h;
+        auto he = std::remove_if(e.begin() + 1, e.end(), pred);
+        auto d = to_dev(h, exec.target());
+        auto it = hpx::parallel::remove_if(pol, d.begin() + 1, d.end(), pred);
+        HPX_TEST_EQ(static_cast<std::size_t>(it - d.begin()), static_cast<std::size_t>(he - e.begin()));
+        same(to_host(d), e, "remove_if (begin + 1, lambda)", n);
+    }
+    {
+        std::vector<T> e = h;
+        auto he = std::stable_partition(e.begin() + 1, e.end(), pred);
+        auto d = to_dev(h, exec.target());
+        auto it = hpx::parallel::stable_partition(pol, d.begin() + 1, d.end(), pred);
+        HPX_TEST_EQ(static_cast<std::size_t>(it - d.begin()), static_cast<std::size_t>(he - e.begin()));
+        same(to_host(d), e, "stable_partition (begin + 1, lambda)", n);
+    }
+}
+
 void test_sorts(hip::default_executor& exec, std::mt19937_64& gen, std::size_t n) {
     auto pol = ex::par.on(exec);
     std::vector<uint64_t> h(n);
@@ -314,6 +368,8 @@ int hpx_main(int argc, char* argv[]) {
         test_copy_if(exec, gen, n);
         test_sorts(exec, gen, n);
     }
+    test_compaction_misaligned<int64_t>(exec, gen, 70001);  // more than one tile of either type
+    test_compaction_misaligned<int32_t>(exec, gen, 70001);
     if (big) test_big(exec, gen);
     return hpx::finalize();
 }

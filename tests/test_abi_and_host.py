@@ -61,7 +61,7 @@ def test_library_is_gfx950_code_object(tmp_path):
         assert targets and all(t.endswith("gfx950") for t in targets), r.stdout
         off = blob.find(b"CCOB", off + total)
         n += 1
-    assert n == 8, n  # runtime elementwise reduce scan copy_if sort merge stencil
+    assert n == 8, n  # runtime elementwise reduce scan compaction sort merge stencil
 
 
 def test_ctypes_table_covers_header():

@@ -410,6 +410,39 @@ def test_copy_if_lookback_groups(pol, gpu_target, dt, n, sel):
         np.testing.assert_array_equal(o.to_host()[off:off + exp.size], exp)
 
 
+def _tile(dt):
+    """Elements per tile of the compaction kernel (compaction_kernel.hpp:
+    1024 threads x 8 rounds x 16 B)."""
+    return 1024 * 8 * 16 // np.dtype(dt).itemsize
+
+
+@pytest.mark.parametrize("off", [0, 1])
+@pytest.mark.parametrize("tiles,extra", [(0, 0), (0, 1), (1, -1), (1, 0), (1, 1), (2, 1), (65, 3)])
+@pytest.mark.parametrize("dt", [np.int32, np.int64, np.float64])
+def test_copy_if_is_partition_copy_accepted_side(pol, gpu_target, dt, tiles, extra, off):
+    """copy_if (the one-sided kernel) against partition_copy's accepted side
+    (the two-sided one) around the tile size.  The output buffer is [one
+    canary | off more | the range | canaries to the end] and is compared whole
+    and bitwise: nothing is stored in front of the range or past count."""
+    n = tiles * _tile(dt) + extra
+    a = rnd(dt, n, 16 + n % 7, *((-1000, 1000) if np.dtype(dt).kind == "i" else ()))
+    mask = a >= 0
+    ut = np.dtype(f"u{np.dtype(dt).itemsize}")
+    blank = np.full(n + 4, -7777, dt)
+    d, o = dev(a, gpu_target), dev(blank, gpu_target)
+    _, end = P.copy_if(pol, d.begin(), d.end(), o.begin() + 1 + off, F.not_less_than(0))
+    count = end - (o.begin() + 1 + off)
+    assert count == np.count_nonzero(mask)
+    exp = blank.copy()
+    exp[1 + off:1 + off + count] = a[mask]
+    got = o.to_host()
+    np.testing.assert_array_equal(got.view(ut), exp.view(ut))
+    ot, of = dev(blank, gpu_target), dev(blank, gpu_target)
+    _, et, _ = P.partition_copy(pol, d.begin(), d.end(), ot.begin(), of.begin(), F.not_less_than(0))
+    assert et - ot.begin() == count
+    np.testing.assert_array_equal(got[1 + off:1 + off + count].view(ut), ot.to_host()[:count].view(ut))
+
+
 def test_copy_if_golden(pol, gpu_target):
     case = golden_cases("copy_if")[0]
     g = load_golden(case)
@@ -636,6 +669,73 @@ def test_copy_if_misaligned_input(pol, gpu_target, dt, off, oout):
     exp = O.copy_if(a[off:], "not_less_than", 0)
     assert end - (o.begin() + oout) == exp.size
     np.testing.assert_array_equal(o.to_host()[oout:oout + exp.size], exp)
+
+
+def _copy_if_at_head_split(pol, gpu_target, dt, off, which):
+    """copy_if on a range that starts off elements past a 16-B boundary, h
+    elements before the next one.  The launcher splits the head off when
+    n > 4 h (compaction_kernel.hpp launch) and loads element by element up to
+    there: sizes on both sides of that switch, a range inside the head, and
+    one of more than a tile behind the head."""
+    total = _tile(dt) + 16
+    a = rnd(dt, total, 43, -1000, 1000)
+    a[off] = 5  # a hit inside the head
+    d, o = dev(a, gpu_target), dev(np.full(total, -7777, dt), gpu_target)
+    first = d.begin() + off
+    h = (16 - first.address % 16) % 16 // np.dtype(dt).itemsize
+    assert h > 0
+    n = {"1": 1, "h": h, "4h": 4 * h, "4h+1": 4 * h + 1, "T+h+1": _tile(dt) + h + 1}[which]
+    _, end = P.copy_if(pol, first, first + n, o.begin(), F.not_less_than(0))
+    exp = O.copy_if(a[off:off + n], "not_less_than", 0)
+    assert end - o.begin() == exp.size
+    got = o.to_host()
+    np.testing.assert_array_equal(got[:exp.size], exp)
+    assert (got[exp.size:] == -7777).all()
+
+
+HEAD_SPLIT_SIZES = ["1", "h", "4h", "4h+1", "T+h+1"]
+
+
+@pytest.mark.parametrize("which", HEAD_SPLIT_SIZES)
+@pytest.mark.parametrize("dt,off", [(np.int32, 1), (np.int32, 2), (np.int32, 3), (np.int64, 1)])
+def test_copy_if_misaligned_head_split_sizes(pol, gpu_target, dt, off, which):
+    _copy_if_at_head_split(pol, gpu_target, dt, off, which)
+
+
+@pytest.mark.parametrize("which", HEAD_SPLIT_SIZES)
+def test_copy_if_misaligned_head_split_sizes_state64(pol, gpu_target, which, monkeypatch):
+    monkeypatch.setenv("HPXHIP_COPY_IF_STATE64", "1")
+    _copy_if_at_head_split(pol, gpu_target, np.int32, 1, which)
+
+
+@pytest.mark.parametrize("out_byte", [0, 2])
+def test_copy_if_input_not_element_aligned(gpu_target, out_byte):
+    """hpxhip_copy_if accepts an input that is not element-aligned (int32
+    values one byte past a 4-byte boundary): no head makes it 16-B aligned, so
+    the kernel loads element by element; more than one tile.  The output is
+    element-aligned or two bytes off; its buffer is compared whole, bytewise."""
+    from hpx_amd import _lib as L
+    import ctypes
+    n = _tile(np.int32) + 5
+
+    def at_byte(x, k):  # an int32 array whose bytes from byte k on are x's
+        raw = np.zeros(4 * (x.size + 1), np.uint8)
+        raw[k:k + 4 * x.size] = x.view(np.uint8)
+        return raw.view(np.int32)
+
+    a = rnd(np.int32, n, 47, -1000, 1000)
+    blank = at_byte(np.full(n, -7777, np.int32), out_byte)
+    d, o = dev(at_byte(a, 1), gpu_target), dev(blank, gpu_target)
+    count = hpx.vector(2, dtype=np.uint64, tgt=gpu_target)
+    vp = ctypes.c_void_p
+    L.call("hpxhip_copy_if", L.I32, L.P_NOT_LT, L.scalar_buf(L.I32, 0), vp(d.data() + 1), vp(o.data() + out_byte), n,
+           vp(count.data()), gpu_target.stream, None, 0)
+    L.call("hpxhip_stream_synchronize", gpu_target.stream)
+    exp = O.copy_if(a, "not_less_than", 0)
+    assert int(count.to_host()[0]) == exp.size
+    want = blank.view(np.uint8).copy()
+    want[out_byte:out_byte + 4 * exp.size] = exp.view(np.uint8)
+    np.testing.assert_array_equal(o.to_host().view(np.uint8), want)
 
 
 # ---- mutually misaligned elementwise ranges (inputs offset from the output

@@ -1,5 +1,5 @@
 """partition_copy, stable_partition / partition and the remove family on the
-GPU (hpxhip_partition_copy, hpxhip_stable_partition, partition_kernel.hpp)
+GPU (hpxhip_partition_copy, hpxhip_stable_partition, compaction_kernel.hpp)
 against numpy: with m the predicate on the host array, the accepted side is
 ``a[m]``, the rejected side ``a[~m]``, the stable partition
 ``np.concatenate((a[m], a[~m]))``.  Every buffer is compared whole and
@@ -22,8 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
-# Elements per tile: partition_detail::tile_elems<T>() in
-# include/hpxhip/kernels/partition_kernel.hpp (kThreads = 1024 threads x
+# Elements per tile: compaction_detail::tile_elems<T>() in
+# include/hpxhip/kernels/compaction_kernel.hpp (kThreads = 1024 threads x
 # kRounds = 8 vectors of 16 B per lane = 128 KiB).
 T8 = 16384   # 8-byte elements
 T4 = 32768   # 4-byte elements

@@ -24,10 +24,11 @@ PLUS, MULTIPLIES, MIN, MAX, BIT_AND, BIT_OR, BIT_XOR = range(7)
 U_IDENTITY, U_SCALE, U_ADD_SCALAR, U_AFFINE, U_NEGATE, U_ABS, U_SQUARE = range(7)
 B_ADD, B_TRIAD, B_SUB, B_MUL, B_AXPY, B_MIN, B_MAX = range(7)
 P_LT, P_LE, P_GT, P_GE, P_EQ, P_NE, P_NOT_LT, P_BITS = range(8)
+Q_EQUAL, Q_EQUAL_SHR = range(2)
 H2H, H2D, D2H, D2D, DEFAULT = range(5)
 GEN_IOTA, GEN_BITS, GEN_RANGE, GEN_UNIT = range(4)
 (ALGO_REDUCE, ALGO_SCAN, ALGO_COPY_IF, ALGO_SORT, ALGO_SORT_BY_KEY, ALGO_MERGE, ALGO_MERGE_RUNS,
- ALGO_REDUCE_BY_KEY, ALGO_PARTITION_COPY, ALGO_STABLE_PARTITION) = range(10)
+ ALGO_REDUCE_BY_KEY, ALGO_PARTITION_COPY, ALGO_STABLE_PARTITION, ALGO_UNIQUE_COPY) = range(11)
 STENCIL_MAX_FUSED = 16  # HPXHIP_STENCIL_MAX_FUSED
 
 SUCCESS = 0
@@ -162,6 +163,7 @@ SIGNATURES = {
     "hpxhip_copy_if": [_i, _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_partition_copy": [_i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_stable_partition": [_i, _i, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
+    "hpxhip_unique_copy": [_i, _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_reduce_by_key": [_i, _i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_sort": [_i, _vp, _u64, _i, _vp, _vp, _sz],
     "hpxhip_sort_by_key": [_i, _i, _vp, _vp, _u64, _i, _vp, _vp, _sz],

@@ -23,6 +23,8 @@ calls one whole-algorithm entry point of the C ABI (include/hpxhip.h):
   stable_partition/partition partition.hpp:292, 1063
   remove_copy(_if)           remove_copy.hpp:173, 350
   remove(_if)                remove.hpp:290, 367
+  unique / unique_copy       unique.hpp:311, 612 (one pass instead of the
+                             reference's three)
   generate (splitmix/iota)   generate.hpp (device generator functors)
   for_loop / for_loop_n      for_loop.hpp:808; for_loop_strided 604,
   for_loop_n_strided         1014 (inductions: for_loop_induction.hpp;
@@ -327,6 +329,57 @@ def remove_if(pol, first, last, pred):
 def remove(pol, first, last, value):
     """remove.hpp:290: remove_copy in place."""
     return remove_if(pol, first, last, F.equal_to(value))
+
+
+# ------------------------------------------------------ unique / unique_copy
+def _unique_call(what, pol, first, last, dest, pred):
+    """One hpxhip_unique_copy call -> (stream, tgt, is_task, count thunk).
+    Every argument check comes before the first device call."""
+    _exec_of(pol)
+    if pred is not None and not isinstance(pred, (F.KeyCompare, F.KeyCompareShifted)):
+        F.require(pred, F.KeyCompare, what)
+    n = _check_range(first, last)
+    if not isinstance(dest, iterator):
+        raise TypeError(f"{what}: expected device iterators (hpx_amd.compute.iterator)")
+    if dest.dtype != first.dtype:
+        raise TypeError(f"{what}: source and destination dtypes differ")
+    kind, arg = L.Q_EQUAL, None
+    if isinstance(pred, F.KeyCompareShifted):
+        if first.dtype in (L.F32, L.F64):
+            raise TypeError(f"{what}: key_equal_shifted needs an integer vector")
+        if not 0 <= pred.bits < 8 * L.DTYPE_SIZE[first.dtype]:
+            raise ValueError(f"{what}: shift {pred.bits} outside [0, {8 * L.DTYPE_SIZE[first.dtype]})")
+        kind, arg = L.Q_EQUAL_SHR, L.scalar_buf(L.I32, pred.bits)
+    stream, tgt, is_task = _context(pol, first, dest)
+    dev, host = _slots_for(tgt).next()
+    L.call("hpxhip_unique_copy", first.dtype, kind, arg, _vp(first.address), _vp(dest.address), n, _vp(dev), stream,
+           None, 0)
+    L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8, L.D2H, stream)
+    return stream, tgt, is_task, lambda: _read_host(host, L.U64)
+
+
+def unique_copy(pol, first, last, dest, pred=None):
+    """unique.hpp:612: element i is kept iff i == 0 or
+    not pred(first[i - 1], first[i]); the kept elements go to dest in input
+    order (the first of each run survives); returns (last, dest_end), or its
+    future under par(task).  pred is std::equal_to (None or F.key_equal) or
+    F.key_equal_shifted(bits).  equal_to compares floats by value:
+    -0.0 == +0.0 collapses and keeps the first, every NaN is kept.  Each
+    element is compared with its immediate predecessor: std::unique_copy for
+    every equivalence relation; for other relations the reference compares
+    with the last kept element (and under par with the element before each
+    chunk).  dest may be first (exactly aliased)."""
+    stream, tgt, is_task, count = _unique_call("unique_copy", pol, first, last, dest, pred)
+    return _finish(is_task, stream, tgt, lambda: (last, dest + count()))
+
+
+def unique(pol, first, last, pred=None):
+    """unique.hpp:311: unique_copy in place; returns first + kept (also for
+    n <= 1, where the reference returns last, the same iterator).  Only
+    [first, first + kept) is written: the elements from the new end onward
+    keep their old values (the reference leaves them unspecified)."""
+    stream, tgt, is_task, count = _unique_call("unique", pol, first, last, first, pred)
+    return _finish(is_task, stream, tgt, lambda: first + count())
 
 
 # --------------------------------------------------------------- transform
@@ -829,7 +882,8 @@ def _guarded(fn):
 
 
 for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "copy_n", "copy_if", "partition_copy",
-              "stable_partition", "partition", "remove_copy_if", "remove_copy", "remove_if", "remove", "transform",
+              "stable_partition", "partition", "remove_copy_if", "remove_copy", "remove_if", "remove", "unique_copy",
+              "unique", "transform",
               "reduce", "transform_reduce", "inclusive_scan", "exclusive_scan", "transform_inclusive_scan",
               "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge", "for_loop_n", "for_loop",
               "for_loop_n_strided", "for_loop_strided"):

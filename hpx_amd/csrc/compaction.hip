@@ -18,6 +18,12 @@
 // hpxhip_stable_partition: accepted elements compacted in place, rejected
 // ones to scratch, then k_partition_tail reads the count from device memory
 // and copies them to [count, n) -- no host round trip.
+// hpxhip_unique_copy: the one-sided kernel in its adjacent mode (unique.hpp:
+// 311,612).  The reference flags, scans and scatters in three passes; here the
+// hit bit of an element is !rel(element before, element), with the element
+// before taken from registers, a neighbouring lane or one extra load per wave.
+// Traffic as copy_if's: 8 B read + 8 B per kept int64 element.  out == in is
+// unique.
 #include <cstdlib>
 
 #include "internal.hpp"
@@ -41,6 +47,33 @@ bool env_flag(const char* name) {
 
 bool natural(const void* p, size_t elem) { return reinterpret_cast<uintptr_t>(p) % elem == 0; }
 
+// Relations (hpxhip_eqrel).
+template <int KIND, typename T>
+struct eqrel_fn {
+    int a;
+    __host__ __device__ __forceinline__ bool operator()(T x, T y) const {
+        if constexpr (KIND == HPXHIP_Q_EQUAL) return x == y;
+        else return (x >> a) == (y >> a);
+    }
+};
+
+template <typename T, typename F>
+int with_eqrel(int kind, const void* arg, F&& f) {
+    switch (kind) {
+        case HPXHIP_Q_EQUAL: return f(eqrel_fn<HPXHIP_Q_EQUAL, T>{0});
+        case HPXHIP_Q_EQUAL_SHR:
+            if constexpr (std::is_integral_v<T>) {
+                int32_t a = -1;
+                if (arg) __builtin_memcpy(&a, arg, sizeof(a));
+                if (a < 0 || a >= static_cast<int32_t>(8 * sizeof(T))) return HPXHIP_ERROR_INVALID_ARGUMENT;
+                return f(eqrel_fn<HPXHIP_Q_EQUAL_SHR, T>{a});
+            } else {
+                return HPXHIP_ERROR_UNSUPPORTED;
+            }
+        default: return HPXHIP_ERROR_INVALID_ARGUMENT;
+    }
+}
+
 }  // namespace
 
 namespace hpxhip {
@@ -48,6 +81,7 @@ size_t copy_if_scratch_bytes(int dtype, uint64_t n) { return partition_scratch_b
 size_t partition_scratch_bytes(int dtype, uint64_t n, bool stable) {
     return dtype_size(dtype) == 8 ? scratch_total<uint64_t>(n, stable) : scratch_total<uint32_t>(n, stable);
 }
+size_t unique_scratch_bytes(int dtype, uint64_t n) { return partition_scratch_bytes(dtype, n, false); }
 }  // namespace hpxhip
 
 extern "C" int hpxhip_copy_if(int dtype, int pred_kind, const void* pred_arg, const void* in, void* out, uint64_t n,
@@ -132,6 +166,35 @@ extern "C" int hpxhip_stable_partition(int dtype, int pred_kind, const void* pre
                                          cus, env_flag("HPXHIP_PARTITION_STATE64"), s));
             HPXHIP_CHECK(C::launch_tail(rej, d, n, count_dev, cus, s));
             return 0;
+        });
+    });
+}
+
+extern "C" int hpxhip_unique_copy(int dtype, int rel_kind, const void* rel_arg, const void* in, void* out, uint64_t n,
+                                  uint64_t* count_dev, hpxhip_stream stream, void* scratch, size_t scratch_bytes) {
+    HPXHIP_ANNOTATE("hpxhip_unique_copy");
+    if (!count_dev || (n && (!in || !out))) return HPXHIP_ERROR_INVALID_ARGUMENT;
+    const size_t es = dtype_size(dtype);
+    if (es && !(natural(in, es) && natural(out, es))) return HPXHIP_ERROR_INVALID_ARGUMENT;
+    return with_dtype(dtype, [&](auto t) -> int {
+        using T = typename decltype(t)::type;
+        // the relation and the scratch size are checked before the device is touched
+        return with_eqrel<T>(rel_kind, rel_arg, [&](auto rel) -> int {
+            if (n && scratch && scratch_bytes < scratch_total<T>(n, false)) return HPXHIP_ERROR_INVALID_ARGUMENT;
+            hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+            device_guard g(s);
+            if (g.status) return g.status;
+            if (n == 0) {
+                HPXHIP_CHECK(hipMemsetAsync(count_dev, 0, sizeof(uint64_t), s));
+                return 0;
+            }
+            void* ws = nullptr;
+            int rc = resolve_scratch(s, scratch, scratch_bytes, scratch_total<T>(n, false), &ws);
+            if (rc) return rc;
+            return static_cast<int>(C::launch<false, true>(static_cast<const T*>(in), static_cast<T*>(out),
+                                                           static_cast<T*>(nullptr), n, rel, count_dev, ws,
+                                                           device_error_word(s), current_device_info().cus,
+                                                           env_flag("HPXHIP_UNIQUE_STATE64"), s));
         });
     });
 }

@@ -308,6 +308,7 @@ size_t reduce_scratch_bytes(uint64_t n);
 size_t scan_scratch_bytes(int dtype, uint64_t n);
 size_t copy_if_scratch_bytes(int dtype, uint64_t n);
 size_t partition_scratch_bytes(int dtype, uint64_t n, bool stable);
+size_t unique_scratch_bytes(int dtype, uint64_t n);
 size_t reduce_by_key_scratch_bytes(int key_dtype, int value_dtype, uint64_t n);
 size_t sort_scratch_bytes(int key_dtype, int value_dtype, uint64_t n);
 size_t merge_scratch_bytes(uint64_t n);

@@ -531,6 +531,7 @@ int hpxhip_scratch_bytes(int algo, int dtype, int aux_dtype, uint64_t n, size_t*
             return 0;
         case HPXHIP_ALGO_PARTITION_COPY: *bytes = partition_scratch_bytes(dtype, n, false); return 0;
         case HPXHIP_ALGO_STABLE_PARTITION: *bytes = partition_scratch_bytes(dtype, n, true); return 0;
+        case HPXHIP_ALGO_UNIQUE_COPY: *bytes = unique_scratch_bytes(dtype, n); return 0;
         default: return HPXHIP_ERROR_INVALID_ARGUMENT;
     }
 }

@@ -14,6 +14,7 @@ References:
 """
 from __future__ import annotations
 
+import operator
 from dataclasses import dataclass, field
 
 from . import _lib as L
@@ -288,6 +289,24 @@ class KeyCompare:
 # one run, every NaN a run of its own).  Not ``equal_to``: that names the
 # predicate ``x == a`` of copy_if.
 key_equal = KeyCompare("std::equal_to")
+
+
+@dataclass(frozen=True)
+class KeyCompareShifted:
+    """equal_to under the projection ``x >> bits`` (HPXHIP_Q_EQUAL_SHR): two
+    neighbouring integers are related when they fall into the same bucket of
+    2**bits values.  An arithmetic shift for signed types.  unique /
+    unique_copy only."""
+    bits: int
+    name: str = "equal_shifted"
+
+    def __call__(self, a, b):
+        return (a >> self.bits) == (b >> self.bits)
+
+
+def key_equal_shifted(bits) -> KeyCompareShifted:
+    """The relation ``(x >> bits) == (y >> bits)`` of unique / unique_copy."""
+    return KeyCompareShifted(operator.index(bits))
 
 
 def require(obj, cls, what: str):

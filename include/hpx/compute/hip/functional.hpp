@@ -13,6 +13,7 @@
 //   traits::pred<F>    -> HPXHIP_P_*   (copy_if)
 //   traits::compare<F> -> ascending / descending (sort, sort_by_key)
 //   traits::key_equal<F> -> std::equal_to (reduce_by_key's key comparator)
+//   traits::eqrel<F>   -> HPXHIP_Q_*   (unique, unique_copy)
 //
 // A user functor with the same meaning as a built-in one opts in by
 // specialising the trait, e.g. the STREAM benchmark's own
@@ -162,6 +163,16 @@ HPXHIP_PREDICATE(not_equal_to, x != value)
 HPXHIP_PREDICATE(not_less_than, !(x < value))  // copyif_random.cpp:45
 HPXHIP_PREDICATE(any_bits, (x & value) != 0)
 #undef HPXHIP_PREDICATE
+
+// ---- relations (unique / unique_copy) -----------------------------------------
+// equal_to under the projection x >> bits: two integers are related when they
+// fall into the same bucket of 2^bits values (HPXHIP_Q_EQUAL_SHR; an
+// arithmetic shift for signed T).  0 <= bits < the bits of T.
+template <typename T>
+struct equal_shifted {
+    int bits;
+    HPX_HOST_DEVICE bool operator()(T x, T y) const { return (x >> bits) == (y >> bits); }
+};
 }  // namespace functional
 
 namespace traits {
@@ -173,6 +184,7 @@ template <typename F, typename Enable = void> struct binop;
 template <typename F, typename Enable = void> struct pred;
 template <typename F, typename Enable = void> struct compare;
 template <typename F, typename Enable = void> struct key_equal;
+template <typename F, typename Enable = void> struct eqrel;
 
 namespace detail {
 template <int K>
@@ -255,12 +267,26 @@ template <typename T> struct compare<std::greater<T>> { static constexpr bool de
 // reduce_by_key's comp: std::equal_to<T> and std::equal_to<> (= equal_to<void>)
 template <typename T> struct key_equal<std::equal_to<T>> {};
 
+// unique's relation: std::equal_to<T>, std::equal_to<> and equal_shifted<T>
+// over elements of type T (on<T>)
+template <typename U> struct eqrel<std::equal_to<U>> {
+    static constexpr int kind = HPXHIP_Q_EQUAL;
+    template <typename T> static constexpr bool on = std::is_void<U>::value || std::is_same<U, T>::value;
+    static int32_t arg(std::equal_to<U> const&) { return 0; }
+};
+template <typename U> struct eqrel<functional::equal_shifted<U>> {
+    static constexpr int kind = HPXHIP_Q_EQUAL_SHR;
+    template <typename T> static constexpr bool on = std::is_same<U, T>::value;
+    static int32_t arg(functional::equal_shifted<U> const& f) { return static_cast<int32_t>(f.bits); }
+};
+
 template <typename F> using unary_t = unary<typename std::decay<F>::type>;
 template <typename F> using binary_t = binary<typename std::decay<F>::type>;
 template <typename F> using binop_t = binop<typename std::decay<F>::type>;
 template <typename F> using pred_t = pred<typename std::decay<F>::type>;
 template <typename F> using compare_t = compare<typename std::decay<F>::type>;
 template <typename F> using key_equal_t = key_equal<typename std::decay<F>::type>;
+template <typename F> using eqrel_t = eqrel<typename std::decay<F>::type>;
 
 // Arithmetic type of a transform: the trait's compute_type, else the
 // functor's (triad_step<double> over int vectors computes in double,

@@ -1,3 +1,4 @@
 // hpx/include/parallel_algorithm.hpp -- forwards to the HIP backend's algorithm layer.
 #pragma once
 #include <hpx/parallel/algorithms.hpp>
+#include <hpx/include/parallel_unique.hpp>

@@ -22,6 +22,8 @@
 //   stable_partition, partition  partition.hpp:292, 1063      -> Iter
 //   remove_copy, remove_copy_if  remove_copy.hpp:173, 350     -> tagged_pair<in, out>
 //   remove, remove_if            remove.hpp:290, 367          -> Iter
+//   unique_copy                  unique.hpp:612               -> tagged_pair<in, out>
+//   unique                       unique.hpp:311               -> Iter
 //
 // Synchronous policies (seq, par, par_unseq) return the value after the
 // target's stream is synchronised (the reference's bulk_sync_execute,
@@ -552,6 +554,92 @@ template <typename P, typename It, typename V>
 detail::result_t<P, It> remove(P&& p, It first, It last, V const& value) {
     using T = detail::value_t<It>;
     return remove_if(std::forward<P>(p), first, last, compute::hip::functional::equal_to<T>{static_cast<T>(value)});
+}
+
+// ------------------------------------------------------ unique / unique_copy
+// unique.hpp:612 unique_copy(policy, first, last, dest, pred = equal_to,
+// proj = identity) -> tagged_pair<in, out> = (last, dest + count).  Element i
+// is kept iff i == 0 or !pred(proj(first[i - 1]), proj(first[i])); the kept
+// elements are written in input order, so the first element of each run
+// survives.  One pass (the compaction kernel in its adjacent mode,
+// hpxhip/kernels/compaction_kernel.hpp) instead of the reference's flags,
+// scan and scatter.  Every element is compared with its immediate
+// predecessor: that equals std::unique_copy and the reference's
+// sequential_unique_copy (:333-356) for every equivalence relation and for
+// every relation that implies value equality.  For other relations the
+// reference compares with the last *kept* element (under `par` with the
+// element before each chunk, so its result depends on the chunking); here it
+// is always the predecessor.  std::equal_to compares floats by value:
+// -0.0 == +0.0 collapses and keeps the first, every NaN is kept.
+// std::equal_to<T>, std::equal_to<> and functional::equal_shifted<T> without
+// a projection run the library's kernels; any other HPX_HOST_DEVICE predicate
+// or projection runs the same kernel as a device closure (hipcc).  dest may
+// be first (exactly aliased).
+template <typename T, typename Pred, typename Proj>
+constexpr bool is_mapped_rel() {
+    if constexpr (detail::tr::detail::is_complete<detail::tr::eqrel_t<Pred>>::value &&
+                  std::is_same<std::decay_t<Proj>, util::projection_identity>::value)
+        return detail::tr::eqrel_t<Pred>::template on<T>;
+    else return false;
+}
+
+template <typename T, typename Tgt, typename Pred, typename Proj>
+void unique_dispatch(char const* what, Tgt const& t, T const* in, T* out, uint64_t n, Pred const& pred,
+                     Proj const& proj, uint64_t* count_dev) {
+    if constexpr (is_mapped_rel<T, Pred, Proj>()) {
+        using Tr = detail::tr::eqrel_t<Pred>;
+        const int32_t arg = Tr::arg(pred);
+        detail::check(hpxhip_unique_copy(detail::dt<T>, Tr::kind, &arg, in, out, n, count_dev, t.stream(), nullptr, 0),
+                      what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::unique_copy(t, in, out, n, pred, proj, count_dev);
+#else
+        detail::no_device_mapping<Pred>(what);
+#endif
+    }
+}
+
+template <typename P, typename In, typename Out, typename Pred = std::equal_to<>,
+          typename Proj = util::projection_identity>
+detail::result_t<P, util::tagged_pair<In, Out>> unique_copy(P&& p, In first, In last, Out dest, Pred&& pred = Pred(),
+                                                            Proj&& proj = Proj()) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out>, "unique_copy: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out>>::value, "unique_copy: the output holds the input's value type");
+    using R = util::tagged_pair<In, Out>;
+    auto const& t = detail::target_of(p, first);
+    uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    unique_dispatch<T>("unique_copy", t, static_cast<T const*>(first.device_ptr()),
+                       static_cast<T*>(dest.device_ptr()), n, pred, proj, static_cast<uint64_t*>(slot.device()));
+    detail::fetch_slot(t, slot, 8, "unique_copy count");
+    return detail::finish_slot<R>(p, t, std::move(slot), [last, dest](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return R{last, dest + static_cast<std::ptrdiff_t>(c)};
+    });
+}
+
+// unique.hpp:311: unique_copy in place -> first + count (also for n <= 1,
+// where the reference returns last, the same iterator).  Only [first, first +
+// count) is written: the elements from the new end onward keep their values
+// (the reference leaves them unspecified).
+template <typename P, typename It, typename Pred = std::equal_to<>, typename Proj = util::projection_identity>
+detail::result_t<P, It> unique(P&& p, It first, It last, Pred&& pred = Pred(), Proj&& proj = Proj()) {
+    static_assert(detail::is_dev<It>, "unique: device iterators required");
+    using T = detail::value_t<It>;
+    auto const& t = detail::target_of(p, first);
+    uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    unique_dispatch<T>("unique", t, static_cast<T const*>(first.device_ptr()), static_cast<T*>(first.device_ptr()), n,
+                       pred, proj, static_cast<uint64_t*>(slot.device()));
+    detail::fetch_slot(t, slot, 8, "unique count");
+    return detail::finish_slot<It>(p, t, std::move(slot), [first](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return first + static_cast<std::ptrdiff_t>(c);
+    });
 }
 
 // ------------------------------------------------------------- transform
@@ -1383,6 +1471,8 @@ HPXHIP_GUARDED_ALGORITHM(remove_copy_if)
 HPXHIP_GUARDED_ALGORITHM(remove_copy)
 HPXHIP_GUARDED_ALGORITHM(remove_if)
 HPXHIP_GUARDED_ALGORITHM(remove)
+HPXHIP_GUARDED_ALGORITHM(unique_copy)
+HPXHIP_GUARDED_ALGORITHM(unique)
 HPXHIP_GUARDED_ALGORITHM(transform)
 HPXHIP_GUARDED_ALGORITHM(reduce)
 HPXHIP_GUARDED_ALGORITHM(transform_reduce)
@@ -1442,6 +1532,8 @@ using parallel::v1::is_sorted;
 using parallel::v1::sort;
 using parallel::v1::sort_by_key;
 using parallel::v1::transform;
+using parallel::v1::unique;
+using parallel::v1::unique_copy;
 using parallel::v1::transform_exclusive_scan;
 using parallel::v1::transform_inclusive_scan;
 using parallel::v1::transform_reduce;

@@ -14,6 +14,7 @@
 //   scans                      scan_kernel.hpp     (single pass, decoupled
 //                                                   look-back, 16-B tiles)
 //   copy_if, partition_copy, stable_partition, remove_copy_if, remove_if
+//   unique, unique_copy
 //                              compaction_kernel.hpp (ballot ranks, look-back;
 //                                                   one- and two-sided)
 //   reduce_by_key              reduce_by_key_kernel.hpp (segmented look-back)
@@ -282,6 +283,33 @@ void stable_partition(compute::hip::target const& t, T* data, uint64_t n, Pred c
                   "stable_partition (device closure)");
     const hipError_t e = C::launch_tail(static_cast<T const*>(rejected), data, n, count_dev, cus_of(t), stream_of(t));
     if (e != hipSuccess) throw hpx::kernel_error(static_cast<int>(e), "stable_partition (device closure)");
+}
+
+// ------------------------------------------------------ unique / unique_copy
+// unique.hpp:311,612 with any binary predicate and projection: the library's
+// compaction kernel in its adjacent mode through the library's launcher.
+// Element i is kept iff i == 0 or !pred(proj(in[i - 1]), proj(in[i])); out may
+// be exactly in (unique).
+template <typename T, typename Pred, typename Proj>
+struct as_projected_rel {
+    Pred pred;
+    Proj proj;
+    __device__ __forceinline__ bool operator()(T const& a, T const& b) const {
+        return static_cast<bool>(pred(proj(a), proj(b)));
+    }
+};
+
+template <typename T, typename Pred, typename Proj>
+void unique_copy(compute::hip::target const& t, T const* in, T* out, uint64_t n, Pred const& pred, Proj const& proj,
+                 uint64_t* count_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "unique (device closure): 4- or 8-byte element types");
+    void* ws = scratch(t, K::compaction_detail::state_bytes<T>(n), "unique scratch");
+    using R = as_projected_rel<T, std::decay_t<Pred>, std::decay_t<Proj>>;
+    const hipError_t e = K::compaction_detail::launch<false, true>(in, out, static_cast<T*>(nullptr), n, R{pred, proj},
+                                                                   count_dev, ws, error_word(t), cus_of(t), false,
+                                                                   stream_of(t));
+    if (e != hipSuccess)
+        throw hpx::kernel_error(static_cast<int>(e), std::string("unique (device closure): ") + hipGetErrorString(e));
 }
 
 // ------------------------------------------------------------ reduce_by_key

@@ -114,6 +114,12 @@ enum hpxhip_pred {
     HPXHIP_P_BITS = 7    /* (x & a) != 0, integers only                        */
 };
 
+/* Relations for unique_copy: rel(x, y) on neighbouring elements. */
+enum hpxhip_eqrel {
+    HPXHIP_Q_EQUAL = 0,     /* x == y (std::equal_to; floats by value)                    */
+    HPXHIP_Q_EQUAL_SHR = 1  /* (x >> a) == (y >> a): integers only, 0 <= a < bits of T;   */
+};                          /* equal_to under the projection x >> a (same bucket)         */
+
 enum hpxhip_memcpy_kind {
     HPXHIP_H2H = 0,
     HPXHIP_H2D = 1,
@@ -133,7 +139,8 @@ enum hpxhip_algo {
     HPXHIP_ALGO_MERGE_RUNS = 6, /* n = the runs' total (hpxhip_merge_runs, up to 8 runs) */
     HPXHIP_ALGO_REDUCE_BY_KEY = 7, /* dtype = the key dtype, aux_dtype = the value dtype */
     HPXHIP_ALGO_PARTITION_COPY = 8,
-    HPXHIP_ALGO_STABLE_PARTITION = 9 /* the tile state plus n elements */
+    HPXHIP_ALGO_STABLE_PARTITION = 9, /* the tile state plus n elements */
+    HPXHIP_ALGO_UNIQUE_COPY = 10
 };
 
 typedef struct hpxhip_stream_opaque* hpxhip_stream; /* == hipStream_t */
@@ -369,6 +376,35 @@ int hpxhip_partition_copy(int dtype, int pred_kind, const void* pred_arg, const 
 int hpxhip_stable_partition(int dtype, int pred_kind, const void* pred_arg, void* data, uint64_t n,
                             uint64_t* count_dev, hpxhip_stream stream, void* scratch,
                             size_t scratch_bytes);
+
+/* ------------------------------------------------- unique / unique_copy */
+/* unique.hpp:311,612: element i of in[0, n) is kept iff i == 0 or
+   !rel(in[i - 1], in[i]); the kept elements go to out in input order (the
+   first element of each run survives) and *count_dev (uint64, device)
+   receives their number, so unique_copy returns (in + n, out + count) and
+   unique returns in + count, also for n <= 1.  One pass over the single-pass
+   compaction kernel, no flag array in memory.  Every element is compared with
+   its immediate predecessor: that is std::unique_copy and the reference's
+   sequential_unique_copy (:333-356) for every equivalence relation and for
+   every relation that implies value equality.  For other relations the
+   reference compares with the last *kept* element (sequentially; under `par`
+   with the element before each chunk, so its result depends on the chunking),
+   this call with the predecessor.  HPXHIP_Q_EQUAL compares by value
+   (std::equal_to: integers bitwise; floats by value, so -0.0 == +0.0
+   collapses and keeps the first, and every NaN is kept).  HPXHIP_Q_EQUAL_SHR:
+   rel_arg points to one int32 (host), the shift a; an arithmetic shift for
+   signed types.  rel_arg is ignored for HPXHIP_Q_EQUAL.
+   out may be exactly `in` (unique; partial overlap is not supported): then
+   only [0, count) is written and the elements from the new end onward keep
+   their values.  n == 0 writes *count_dev = 0 and nothing else.
+   INVALID_ARGUMENT: a null count, null in / out with n > 0, pointers not
+   aligned to the element, an unknown rel_kind, a shift outside [0, bits),
+   scratch too small.  UNSUPPORTED: EQUAL_SHR on F32 / F64.
+   HPXHIP_UNIQUE_STATE64=1 forces the 64-bit look-back value (read per call).
+   Scratch: HPXHIP_ALGO_UNIQUE_COPY. */
+int hpxhip_unique_copy(int dtype, int rel_kind, const void* rel_arg, const void* in, void* out,
+                       uint64_t n, uint64_t* count_dev, hpxhip_stream stream,
+                       void* scratch, size_t scratch_bytes);
 
 /* ------------------------------------------------------ reduce_by_key */
 /* reduce_by_key.hpp:586: a run is a maximal range of consecutive equal keys

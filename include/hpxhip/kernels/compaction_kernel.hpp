@@ -1,6 +1,7 @@
 // compaction_kernel.hpp -- single-pass, stable stream compaction: the kernel
-// and its host launcher for copy_if (one-sided) and for partition_copy,
-// stable_partition, remove_copy_if and remove_if (two-sided); see
+// and its host launcher for copy_if (one-sided), for partition_copy,
+// stable_partition, remove_copy_if and remove_if (two-sided) and for
+// unique_copy and unique (one-sided, adjacent mode); see
 // hpx_amd/csrc/compaction.hip for the entry points.  Header so that the
 // library and the device-closure layer (hpx/parallel/detail/
 // device_algorithms.hpp) instantiate the same kernel through the same
@@ -38,6 +39,34 @@
 // stored and out_false is ignored.  TWO_SIDED: either output may be null (a
 // uniform run-time branch): that side is ranked and staged but not stored.
 //
+// Adjacent mode (ADJ = true, compile-time, one-sided; unique_copy, and unique
+// with out == in): the predicate is a binary relation rel and the hit bit of
+// element i is !rel(in[i - 1], in[i]); the range's first element has no
+// element before it and is a hit.  Every element is compared with its
+// immediate predecessor (std::unique_copy for equivalence relations; the
+// reference compares with the last kept element).  The tile's index order is
+// (wave, round, lane, element), wbase + (r * 64 + lane) * V + e, so the
+// element before comes from
+//   x[r].v[e - 1]                       for e > 0,
+//   the previous lane's v[V - 1]        for e == 0 (DPP wave_shr:1),
+//   lane 63 of round r - 1              for lane 0 (readlane),
+//   in[wbase - 1]                       for lane 0 of round 0: one extra
+//     element load per wave (lane 0), issued in load(t) in front of the wave's
+//     vector loads -- the early next-tile load included -- and held in a
+//     register until the hit bits are formed.  For wave 0 that is the last
+//     element of the previous tile, for tile 0 behind a split-off head
+//     in[-1], the head's last element.
+// The other source of the previous wave's last element, a hand-over through
+// LDS (lane 63 writes, a barrier, lane 0 of the next wave reads; only thread 0
+// loads in[tile_base - 1]), puts a workgroup barrier in front of the hit bits.
+// Both were measured (profiles/unique_ubench.log against
+// unique_ubench_lds_handover.log); the load per wave is shipped.  Everything else -- tile claim, ranks, stage, pipelined
+// load, look-back, store_run, the launcher -- is the code copy_if runs; the
+// other instantiations compile to the same registers, spills and LDS as
+// before (profiles/unique_resource_usage.txt).  A separate kernel was not
+// needed.  Element-wise loads and partial tiles: a padded position is never a
+// hit and never the element before a valid one (it lies behind all of them).
+//
 // Aliasing.  Each output may be exactly the input (not both; the outputs must
 // not overlap each other).  This covers the one-sided form: copy_if with
 // out == in is the out_true == in case.  Why no tile overwrites input that is
@@ -61,6 +90,29 @@
 //   sees the caller's values wherever it falls in time.
 //   In place only [0, count) of the aliased output is stored; the elements
 //   from the new end onward are not touched.
+//   Adjacent mode, out_true == in (unique).  (a)-(c) hold unchanged: the
+//   destination index is at most the source index.  New are the reads of
+//   in[wbase - 1]:
+//   - wave > 0: the element lies in the tile's own range, and the argument
+//     for the tile's own loads covers it (early load included).
+//   - wave 0 of tile u > 0 reads in[u * TILE - 1], which tile u - 1 owns.
+//     A tile t < u - 1 stores only below (t + 1) * TILE <= (u - 1) * TILE.
+//     Tile u - 1 stores below u * TILE, and by (c) the only element it can
+//     store AT u * TILE - 1 is the one whose source is that index, when
+//     nothing before it was dropped: the same bytes.  Tiles from u on store
+//     only after their look-back, i.e. after u has published its aggregate,
+//     and that aggregate depends on this load: it is the operand of element
+//     0's hit bit, which enters the wave count, the tile count and so the
+//     value given to st.publish.  The dependence is a data dependence in the
+//     code below (bnd -> hit -> wave_count -> agg), not a convention.
+//   - tile 0 behind a split-off head reads in[-1], the head's last element.
+//     k_compact_head runs before this kernel on the same stream; in place it
+//     stores out_true[c] with c <= i, so position h - 1 can only receive the
+//     element h - 1 itself.  Within this kernel in[-1] lies below every
+//     tile's range: tile 0 stores after its own barrier (B), later tiles
+//     after tile 0 has published, both after the load was consumed.
+//   The head kernel keeps the element before in a register, so its own
+//   in-place stores (destination <= source) never feed a comparison.
 #pragma once
 
 #include <hpxhip/kernels/common.hpp>
@@ -140,8 +192,11 @@ __device__ __forceinline__ void store_run(T* o, const T* stage, uint32_t cnt) {
 // 2.138-2.146 ms, profiles/r04_ubench_lookback_onehop.log).
 // *count_dev <- accepted elements, the head's included.
 // Grid: at most one workgroup per CU, at most ntiles.
+// ADJ (one-sided only): pred is a binary relation and element i is accepted
+// iff it has no element before it or !pred(in[i - 1], in[i]) (the head note
+// above); in[-1] is read when head > 0.
 template <typename T, typename Pred, bool ALIGNED, typename SV, bool TWO_SIDED, int MINW = 4, int ROUNDS = kRounds,
-          int OUT_ALIGN = 128>
+          int OUT_ALIGN = 128, bool ADJ = false>
 __global__ __launch_bounds__(kThreads, MINW) void k_compact(const T* in, T* out_true, T* out_false, uint64_t n,
                                                             uint64_t head, Pred pred, uint64_t* count_dev,
                                                             uint32_t* counter, tile_state<SV> st, uint64_t ntiles,
@@ -152,6 +207,7 @@ __global__ __launch_bounds__(kThreads, MINW) void k_compact(const T* in, T* out_
     using VT = vec<T, V>;
     using H = hit_word<ROUNDS * V>;
     static_assert(ROUNDS * V <= 64, "hit bits per lane");
+    static_assert(!(ADJ && TWO_SIDED), "the adjacent mode is one-sided");
 
     __shared__ T s_stage[TILE];
     __shared__ uint32_t s_wave_total[kWaves];
@@ -166,8 +222,14 @@ __global__ __launch_bounds__(kThreads, MINW) void k_compact(const T* in, T* out_
             s_next = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     };
     VT x[ROUNDS];
+    [[maybe_unused]] T bnd{};  // ADJ, lane 0: the element before the wave's first
     auto load = [&](uint64_t t) {
         const uint64_t wbase = t * TILE + wlocal;
+        if constexpr (ADJ) {
+            // the previous wave's, the previous tile's or the head's last
+            // element; issued with the wave's own loads, held until the hit bits
+            if (lane == 0 && wbase < n && (wbase > 0 || head > 0)) bnd = (in + wbase)[-1];
+        }
         if (ALIGNED && wbase + WAVE_ELEMS <= n) {
             const VT* src = reinterpret_cast<const VT*>(in + wbase);
 #pragma unroll
@@ -203,7 +265,31 @@ __global__ __launch_bounds__(kThreads, MINW) void k_compact(const T* in, T* out_
             else return wbase + (static_cast<uint64_t>(r) * kWave + lane) * V + e < n;
         };
         H hit = 0;
-        if (TWO_SIDED ? valid == TILE : wbase + WAVE_ELEMS <= n) {
+        if constexpr (ADJ) {
+            // The element before (r, lane, e) in index order: x[r].v[e - 1];
+            // e == 0: the previous lane's last (DPP wave_shr:1); lane 0: lane
+            // 63 of the previous round; lane 0 of round 0: bnd.  The range's
+            // first element has none and is kept.  A padded position is never
+            // a hit, and none precedes a valid element (index order).
+            const bool first = head == 0 && wbase == 0 && lane == 0;
+            auto adjacent_hits = [&](auto bounded) {
+#pragma unroll
+                for (int r = 0; r < ROUNDS; ++r) {
+                    T old = bnd;
+                    if (r > 0) old = readlane(x[r - 1].v[V - 1], kWave - 1);
+                    const T before = dpp<DPP_WAVE_SHR1>(old, x[r].v[V - 1]);
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        bool h = !pred(e == 0 ? before : x[r].v[e > 0 ? e - 1 : 0], x[r].v[e]);
+                        if (r == 0 && e == 0) h = h || first;
+                        if constexpr (decltype(bounded)::value) h = h && inside(r, e);
+                        hit |= static_cast<H>(h) << (r * V + e);
+                    }
+                }
+            };
+            if (wbase + WAVE_ELEMS <= n) adjacent_hits(std::false_type{});
+            else adjacent_hits(std::true_type{});
+        } else if (TWO_SIDED ? valid == TILE : wbase + WAVE_ELEMS <= n) {
 #pragma unroll
             for (int r = 0; r < ROUNDS; ++r)
 #pragma unroll
@@ -290,14 +376,23 @@ __global__ __launch_bounds__(kThreads, MINW) void k_compact(const T* in, T* out_
 // Head of a misaligned input (fewer than 16 B of elements), placed by one
 // thread: accepted -> out_true[0..c), rejected -> out_false[0..h - c),
 // c -> *count; a null output is skipped.  In place: both destinations trail
-// the source index.
-template <typename T, typename Pred>
+// the source index.  ADJ: accepted iff i == 0 or !pred(in[i - 1], in[i]); the
+// element before is kept in a register, so in place it is the caller's value.
+template <typename T, typename Pred, bool ADJ = false>
 __global__ void k_compact_head(const T* in, T* out_true, T* out_false, uint64_t h, Pred pred, uint64_t* count) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     uint64_t c = 0, f = 0;
+    [[maybe_unused]] T before{};
     for (uint64_t i = 0; i < h; ++i) {
         const T v = in[i];
-        if (pred(v)) {
+        bool accept;
+        if constexpr (ADJ) {
+            accept = i == 0 || !pred(before, v);
+            before = v;
+        } else {
+            accept = pred(v);
+        }
+        if (accept) {
             if (out_true) out_true[c] = v;
             ++c;
         } else {
@@ -357,7 +452,7 @@ size_t state_bytes(uint64_t n) {
     return head_count_off<T>(n) + 256;
 }
 
-template <bool TWO_SIDED, bool ALIGNED, typename SV, typename T, typename Pred>
+template <bool TWO_SIDED, bool ALIGNED, typename SV, bool ADJ = false, typename T, typename Pred>
 hipError_t launch_sv(const T* in, T* out_true, T* out_false, uint64_t n, uint64_t head, Pred pred, uint64_t* count_dev,
                      char* ws, uint32_t* err_word, int cus, const uint64_t* prefix0, hipStream_t s) {
     const uint64_t ntiles = ntiles_for<T>(n);
@@ -366,8 +461,8 @@ hipError_t launch_sv(const T* in, T* out_true, T* out_false, uint64_t n, uint64_
     tile_state<SV> st{reinterpret_cast<uint64_t*>(ws + kSlotsOff), err_word};
     // one persistent workgroup per CU (its stage is 128 of the CU's 160 KiB of LDS)
     const uint64_t grid = ntiles < static_cast<uint64_t>(cus) ? ntiles : static_cast<uint64_t>(cus);
-    hipLaunchKernelGGL((k_compact<T, Pred, ALIGNED, SV, TWO_SIDED>), dim3(static_cast<unsigned>(grid)), dim3(kThreads),
-                       0, s, in, out_true, out_false, n, head, pred, count_dev, reinterpret_cast<uint32_t*>(ws), st,
+    hipLaunchKernelGGL((k_compact<T, Pred, ALIGNED, SV, TWO_SIDED, 4, kRounds, 128, ADJ>),
+                       dim3(static_cast<unsigned>(grid)), dim3(kThreads), 0, s, in, out_true, out_false, n, head, pred, count_dev, reinterpret_cast<uint32_t*>(ws), st,
                        ntiles, prefix0);
     return hipGetLastError();
 }
@@ -377,12 +472,15 @@ hipError_t launch_sv(const T* in, T* out_true, T* out_false, uint64_t n, uint64_
 // either output may be null.  ws: state_bytes<T>(n) of scratch, err_word: the
 // device error word the look-back raises, cus: the device's compute units.
 // force64: the 64-bit look-back value at any n (tests).
+// ADJ (one-sided): pred is a binary relation rel, and element i is accepted
+// iff i == 0 or !rel(in[i - 1], in[i]) -- unique_copy, unique with
+// out_true == in.
 // A misaligned input whose elements are naturally aligned: the head (< 16 B)
 // is placed first, the rest takes the vector kernel seeded with the head's
 // count (copy_if, int64 offset by one element: 3.83 -> ~2.4 ms at 2^30,
 // profiles/r02_unaligned_ranges.log).  An input that is not element-aligned,
 // or one no longer than four such heads, is loaded element by element.
-template <bool TWO_SIDED, typename T, typename Pred>
+template <bool TWO_SIDED, bool ADJ = false, typename T, typename Pred>
 hipError_t launch(const T* in, T* out_true, T* out_false, uint64_t n, Pred pred, uint64_t* count_dev, void* ws,
                   uint32_t* err_word, int cus, bool force64, hipStream_t s) {
     if (n == 0) return hipMemsetAsync(count_dev, 0, sizeof(uint64_t), s);
@@ -390,16 +488,16 @@ hipError_t launch(const T* in, T* out_true, T* out_false, uint64_t n, Pred pred,
     const bool sv32 = n < (uint64_t{1} << 32) && !force64;
     auto run = [&](auto aligned, const T* ip, uint64_t m, uint64_t head, const uint64_t* prefix0) {
         constexpr bool A = decltype(aligned)::value;
-        return sv32 ? launch_sv<TWO_SIDED, A, uint32_t>(ip, out_true, out_false, m, head, pred, count_dev, base,
-                                                        err_word, cus, prefix0, s)
-                    : launch_sv<TWO_SIDED, A, uint64_t>(ip, out_true, out_false, m, head, pred, count_dev, base,
-                                                        err_word, cus, prefix0, s);
+        return sv32 ? launch_sv<TWO_SIDED, A, uint32_t, ADJ>(ip, out_true, out_false, m, head, pred, count_dev, base,
+                                                             err_word, cus, prefix0, s)
+                    : launch_sv<TWO_SIDED, A, uint64_t, ADJ>(ip, out_true, out_false, m, head, pred, count_dev, base,
+                                                             err_word, cus, prefix0, s);
     };
     const uint64_t h = head_to_align16(in, sizeof(T));
     if (h == 0) return run(std::true_type{}, in, n, 0, nullptr);
     if (h != UINT64_MAX && n > 4 * h) {
         auto* hc = reinterpret_cast<uint64_t*>(base + head_count_off<T>(n));
-        hipLaunchKernelGGL((k_compact_head<T, Pred>), dim3(1), dim3(64), 0, s, in, out_true,
+        hipLaunchKernelGGL((k_compact_head<T, Pred, ADJ>), dim3(1), dim3(64), 0, s, in, out_true,
                            TWO_SIDED ? out_false : static_cast<T*>(nullptr), h, pred, hc);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;

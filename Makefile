@@ -21,7 +21,7 @@ KHDR     := $(wildcard hpx_amd/csrc/*.hpp) $(wildcard include/hpxhip/kernels/*.h
 ORACLE   := oracle/_build/liboracle.so
 OFLAGS   := -O2 -fPIC -std=c++17 -ffp-contract=off -Wall -pthread
 
-.PHONY: all lib oracle clean cxxtests oracle-sanitize mw-variants
+.PHONY: all lib oracle clean cxxtests oracle-sanitize mw-variants find-walk
 
 # C++ tests of include/hpx (plain g++ host code linked to the C ABI library)
 CXXT     := compute_api algorithms_known_answer stream_hip for_loop_merge stencil_partitioned call_overhead exception_list futures
@@ -39,6 +39,9 @@ oracle: $(ORACLE)
 $(BUILD)/csrc/%.o: hpx_amd/csrc/%.hip $(KHDR)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+# search.hip (the search family) is part of reduce.hip's translation unit
+$(BUILD)/csrc/reduce.o: hpx_amd/csrc/search.hip
 
 $(LIB): $(KOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KOBJ)
@@ -75,6 +78,18 @@ hpx_amd/variants/%/libhpxhip.so: hpx_amd/csrc/merge.hip $(filter-out $(BUILD)/cs
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(filter-out $(BUILD)/csrc/merge.o,$(KOBJ)) \
 	    $(BUILD)/variants/$*/merge.o
 
+# Ablation build of find's other grid (search_kernel.hpp): FWALK
+# blocks that walk the chunks instead of one block per chunk.  Not part of
+# `all`; scripts/ubench/search.py runs against it with HPXHIP_LIB.
+FWALK    ?= 512
+find-walk: hpx_amd/variants/findwalk/libhpxhip.so
+hpx_amd/variants/findwalk/libhpxhip.so: hpx_amd/csrc/reduce.hip hpx_amd/csrc/search.hip \
+                                        $(filter-out $(BUILD)/csrc/reduce.o,$(KOBJ)) $(KHDR)
+	@mkdir -p $(dir $@) $(BUILD)/variants/findwalk
+	$(HIPCC) $(HIPFLAGS) -DHPXHIP_FIND_WALK_BLOCKS=$(FWALK) -c $< -o $(BUILD)/variants/findwalk/reduce.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(filter-out $(BUILD)/csrc/reduce.o,$(KOBJ)) \
+	    $(BUILD)/variants/findwalk/reduce.o
+
 $(ORACLE): oracle/oracle.cpp oracle/oracle.h
 	@mkdir -p $(dir $@)
 	$(CXX) $(OFLAGS) -shared -o $@ oracle/oracle.cpp
@@ -88,7 +103,7 @@ tests/cxx/bin/oracle_sanitize: tests/cxx/oracle_sanitize.cpp oracle/oracle.cpp o
 
 # ... and the hipcc-compiled ones (device closures, HPX_HOST_DEVICE lambdas)
 HIPT     := device_closures partitioned_vector closure_algorithms closure_timing dataflow_stencil bench_targets \
-            reduce_by_key partition unique
+            reduce_by_key partition unique search
 HIPTBIN  := $(HIPT:%=tests/cxx/bin/%)
 HTFLAGS  := -O2 -std=c++17 --offload-arch=$(ARCH) --offload-compress -Wall -Wno-unused-parameter -Iinclude
 

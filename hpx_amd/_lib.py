@@ -25,10 +25,12 @@ U_IDENTITY, U_SCALE, U_ADD_SCALAR, U_AFFINE, U_NEGATE, U_ABS, U_SQUARE = range(7
 B_ADD, B_TRIAD, B_SUB, B_MUL, B_AXPY, B_MIN, B_MAX = range(7)
 P_LT, P_LE, P_GT, P_GE, P_EQ, P_NE, P_NOT_LT, P_BITS = range(8)
 Q_EQUAL, Q_EQUAL_SHR = range(2)
+X_MIN, X_MAX, X_MINMAX = range(3)
 H2H, H2D, D2H, D2D, DEFAULT = range(5)
 GEN_IOTA, GEN_BITS, GEN_RANGE, GEN_UNIT = range(4)
 (ALGO_REDUCE, ALGO_SCAN, ALGO_COPY_IF, ALGO_SORT, ALGO_SORT_BY_KEY, ALGO_MERGE, ALGO_MERGE_RUNS,
  ALGO_REDUCE_BY_KEY, ALGO_PARTITION_COPY, ALGO_STABLE_PARTITION, ALGO_UNIQUE_COPY) = range(11)
+ALGO_COUNT_IF, ALGO_MINMAX_ELEMENT = 12, 13  # 11 is not assigned
 STENCIL_MAX_FUSED = 16  # HPXHIP_STENCIL_MAX_FUSED
 
 SUCCESS = 0
@@ -164,6 +166,10 @@ SIGNATURES = {
     "hpxhip_partition_copy": [_i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_stable_partition": [_i, _i, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_unique_copy": [_i, _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
+    "hpxhip_find_if": [_i, _i, _vp, _i, _vp, _u64, _vp, _vp],
+    "hpxhip_mismatch": [_i, _vp, _vp, _u64, _vp, _vp],
+    "hpxhip_count_if": [_i, _i, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
+    "hpxhip_minmax_element": [_i, _i, _i, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_reduce_by_key": [_i, _i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_sort": [_i, _vp, _u64, _i, _vp, _vp, _sz],
     "hpxhip_sort_by_key": [_i, _i, _vp, _vp, _u64, _i, _vp, _vp, _sz],

@@ -25,6 +25,11 @@ calls one whole-algorithm entry point of the C ABI (include/hpxhip.h):
   remove(_if)                remove.hpp:290, 367
   unique / unique_copy       unique.hpp:311, 612 (one pass instead of the
                              reference's three)
+  find / find_if(_not)       find.hpp:70, 216, 382 (early exit: a hint on the
+  all_of / any_of / none_of  result word, all_any_none.hpp)
+  count / count_if           count.hpp:259, 451
+  min/max/minmax_element     minmax.hpp:46-66, 277, 513-541
+  equal / mismatch           equal.hpp:229, 398, mismatch.hpp:227, 396
   generate (splitmix/iota)   generate.hpp (device generator functors)
   for_loop / for_loop_n      for_loop.hpp:808; for_loop_strided 604,
   for_loop_n_strided         1014 (inductions: for_loop_induction.hpp;
@@ -380,6 +385,171 @@ def unique(pol, first, last, pred=None):
     keep their old values (the reference leaves them unspecified)."""
     stream, tgt, is_task, count = _unique_call("unique", pol, first, last, first, pred)
     return _finish(is_task, stream, tgt, lambda: first + count())
+
+
+# ------------------------------------------------------------ search family
+# find.hpp, all_any_none.hpp, count.hpp, minmax.hpp, equal.hpp, mismatch.hpp:
+# questions asked of a range.  Every call leaves one uint64 (two for
+# minmax_element) in a result slot and reads it back with the stream.
+def _slot_call(name, stream, tgt, *args_before, tail=(), words=1):
+    """Call `name`(*args_before, slot, stream, *tail) and queue the read-back
+    of `words` uint64 -> thunk returning the list of them."""
+    dev, host = _slots_for(tgt).next()
+    L.call(name, *args_before, _vp(dev), stream, *tail)
+    L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8 * words, L.D2H, stream)
+    return lambda: [_read_host(host + 8 * w, L.U64) for w in range(words)]
+
+
+def _find_call(what, pol, first, last, pred, negate):
+    """One hpxhip_find_if call -> (stream, tgt, is_task, n, index thunk).
+    Every argument check comes before the first device call."""
+    _exec_of(pol)
+    pred = F.require(pred, F.Predicate, what)
+    n = _check_range(first, last)
+    arg = L.scalar_buf(first.dtype, pred.arg)
+    stream, tgt, is_task = _context(pol, first)
+    words = _slot_call("hpxhip_find_if", stream, tgt, first.dtype, pred.kind, arg, 1 if negate else 0,
+                       _vp(first.address), n)
+    return stream, tgt, is_task, n, lambda: words()[0]
+
+
+def find_if(pol, first, last, pred):
+    """find.hpp:216: the first iterator whose element satisfies pred, or last
+    (first for an empty range); a future under par(task).  Blocks above a hit
+    that is already known skip their loads."""
+    stream, tgt, is_task, n, index = _find_call("find_if", pol, first, last, pred, False)
+    return _finish(is_task, stream, tgt, lambda: first + index())
+
+
+def find_if_not(pol, first, last, pred):
+    """find.hpp:382: the first iterator whose element does NOT satisfy pred
+    (a NaN fails less_than, so find_if_not(less_than(a)) finds it), or last."""
+    stream, tgt, is_task, n, index = _find_call("find_if_not", pol, first, last, pred, True)
+    return _finish(is_task, stream, tgt, lambda: first + index())
+
+
+def find(pol, first, last, value):
+    """find.hpp:70: the first iterator with ``*it == value`` (by value: 0.0
+    finds -0.0, a NaN is never found), or last."""
+    _exec_of(pol)
+    stream, tgt, is_task, n, index = _find_call("find", pol, first, last, F.equal_to(value), False)
+    return _finish(is_task, stream, tgt, lambda: first + index())
+
+
+def any_of(pol, first, last, pred):
+    """all_any_none.hpp: find_if found something; False for an empty range."""
+    stream, tgt, is_task, n, index = _find_call("any_of", pol, first, last, pred, False)
+    return _finish(is_task, stream, tgt, lambda: index() != n)
+
+
+def none_of(pol, first, last, pred):
+    """all_any_none.hpp: not any_of; True for an empty range."""
+    stream, tgt, is_task, n, index = _find_call("none_of", pol, first, last, pred, False)
+    return _finish(is_task, stream, tgt, lambda: index() == n)
+
+
+def all_of(pol, first, last, pred):
+    """all_any_none.hpp: find_if_not found nothing; True for an empty range."""
+    stream, tgt, is_task, n, index = _find_call("all_of", pol, first, last, pred, True)
+    return _finish(is_task, stream, tgt, lambda: index() == n)
+
+
+def count_if(pol, first, last, pred):
+    """count.hpp:451: the number of elements that satisfy pred (an int); the
+    transform_reduce kernel over ``1 if pred(x) else 0``."""
+    _exec_of(pol)
+    pred = F.require(pred, F.Predicate, "count_if")
+    n = _check_range(first, last)
+    arg = L.scalar_buf(first.dtype, pred.arg)
+    stream, tgt, is_task = _context(pol, first)
+    words = _slot_call("hpxhip_count_if", stream, tgt, first.dtype, pred.kind, arg, _vp(first.address), n,
+                       tail=(None, 0))
+    return _finish(is_task, stream, tgt, lambda: words()[0])
+
+
+def count(pol, first, last, value):
+    """count.hpp:259: the number of elements with ``x == value`` (by value:
+    0.0 counts -0.0, a NaN is never counted)."""
+    _exec_of(pol)
+    return count_if(pol, first, last, F.equal_to(value))
+
+
+def _extreme_call(what, which, pol, first, last, comp):
+    _exec_of(pol)
+    comp = F.require(comp, F.Compare, what)
+    n = _check_range(first, last)
+    stream, tgt, is_task = _context(pol, first)
+    words = _slot_call("hpxhip_minmax_element", stream, tgt, first.dtype, which, 1 if comp.descending else 0,
+                       _vp(first.address), n, tail=(None, 0), words=2 if which == L.X_MINMAX else 1)
+    return stream, tgt, is_task, words
+
+
+def min_element(pol, first, last, comp=F.less):
+    """minmax.hpp:46-66: an iterator to the FIRST smallest element under comp
+    (std::less / std::greater); first for an empty range.  Floats compare by
+    value (-0.0 and +0.0 tie); with NaNs in the range the result is some
+    valid iterator into it, the same one run to run."""
+    stream, tgt, is_task, words = _extreme_call("min_element", L.X_MIN, pol, first, last, comp)
+    return _finish(is_task, stream, tgt, lambda: first + words()[0])
+
+
+def max_element(pol, first, last, comp=F.less):
+    """minmax.hpp:277: an iterator to the FIRST largest element under comp."""
+    stream, tgt, is_task, words = _extreme_call("max_element", L.X_MAX, pol, first, last, comp)
+    return _finish(is_task, stream, tgt, lambda: first + words()[0])
+
+
+def minmax_element(pol, first, last, comp=F.less):
+    """minmax.hpp:513-541: (the FIRST smallest, the LAST largest) in one pass
+    over the range; (first, first) for an empty range."""
+    stream, tgt, is_task, words = _extreme_call("minmax_element", L.X_MINMAX, pol, first, last, comp)
+
+    def pair():
+        lo, hi = words()
+        return first + lo, first + hi
+    return _finish(is_task, stream, tgt, pair)
+
+
+def _mismatch_call(what, pol, first1, last1, first2, last2):
+    """-> (stream, tgt, is_task, n1, n2, index thunk); one hpxhip_mismatch
+    over min(n1, n2) elements (n2 = n1 without last2).  index is None when
+    `what` is equal and the lengths differ: no launch."""
+    _exec_of(pol)
+    n1 = _check_range(first1, last1)
+    if not isinstance(first2, iterator):
+        raise TypeError(f"{what}: expected device iterators (hpx_amd.compute.iterator)")
+    n2 = n1 if last2 is None else _check_range(first2, last2)
+    if first1.dtype != first2.dtype:
+        raise TypeError(f"{what}: the two ranges' dtypes differ")
+    stream, tgt, is_task = _context(pol, first1, first2)
+    if what == "equal" and n1 != n2:
+        return stream, tgt, is_task, n1, n2, None
+    words = _slot_call("hpxhip_mismatch", stream, tgt, first1.dtype, _vp(first1.address), _vp(first2.address),
+                       min(n1, n2))
+    return stream, tgt, is_task, n1, n2, lambda: words()[0]
+
+
+def mismatch(pol, first1, last1, first2, last2=None):
+    """mismatch.hpp:227,396: the first position at which the ranges differ
+    (``!(a == b)`` by value: a NaN differs from itself) as a pair of
+    iterators, over min(n1, n2) elements with four iterators; the ends of
+    what was searched if they agree there."""
+    stream, tgt, is_task, n1, n2, index = _mismatch_call("mismatch", pol, first1, last1, first2, last2)
+
+    def pair():
+        i = index()
+        return first1 + i, first2 + i
+    return _finish(is_task, stream, tgt, pair)
+
+
+def equal(pol, first1, last1, first2, last2=None):
+    """equal.hpp:229,398: True iff the ranges agree element by element (by
+    value); with four iterators ranges of different length are unequal without
+    a launch."""
+    stream, tgt, is_task, n1, n2, index = _mismatch_call("equal", pol, first1, last1, first2, last2)
+    if index is None:
+        return make_ready_future(False) if is_task else False
+    return _finish(is_task, stream, tgt, lambda: index() == n1)
 
 
 # --------------------------------------------------------------- transform
@@ -883,7 +1053,8 @@ def _guarded(fn):
 
 for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "copy_n", "copy_if", "partition_copy",
               "stable_partition", "partition", "remove_copy_if", "remove_copy", "remove_if", "remove", "unique_copy",
-              "unique", "transform",
+              "unique", "find", "find_if", "find_if_not", "all_of", "any_of", "none_of", "count", "count_if",
+              "min_element", "max_element", "minmax_element", "equal", "mismatch", "transform",
               "reduce", "transform_reduce", "inclusive_scan", "exclusive_scan", "transform_inclusive_scan",
               "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge", "for_loop_n", "for_loop",
               "for_loop_n_strided", "for_loop_strided"):

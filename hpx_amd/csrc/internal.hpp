@@ -309,6 +309,8 @@ size_t scan_scratch_bytes(int dtype, uint64_t n);
 size_t copy_if_scratch_bytes(int dtype, uint64_t n);
 size_t partition_scratch_bytes(int dtype, uint64_t n, bool stable);
 size_t unique_scratch_bytes(int dtype, uint64_t n);
+size_t count_if_scratch_bytes(uint64_t n);
+size_t minmax_element_scratch_bytes(uint64_t n);
 size_t reduce_by_key_scratch_bytes(int key_dtype, int value_dtype, uint64_t n);
 size_t sort_scratch_bytes(int key_dtype, int value_dtype, uint64_t n);
 size_t merge_scratch_bytes(uint64_t n);

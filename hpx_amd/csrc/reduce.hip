@@ -162,3 +162,8 @@ int hpxhip_transform_reduce_binary(int in_dtype, int acc_dtype, int red_op, int 
 }
 
 }  // extern "C"
+
+// The search family (find, count, min/max_element, equal, mismatch): further
+// reductions over reduce_kernel.hpp, built into this translation unit so that
+// the library keeps one code object per kernel family.
+#include "search.hip"

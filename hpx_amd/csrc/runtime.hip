@@ -532,6 +532,8 @@ int hpxhip_scratch_bytes(int algo, int dtype, int aux_dtype, uint64_t n, size_t*
         case HPXHIP_ALGO_PARTITION_COPY: *bytes = partition_scratch_bytes(dtype, n, false); return 0;
         case HPXHIP_ALGO_STABLE_PARTITION: *bytes = partition_scratch_bytes(dtype, n, true); return 0;
         case HPXHIP_ALGO_UNIQUE_COPY: *bytes = unique_scratch_bytes(dtype, n); return 0;
+        case HPXHIP_ALGO_COUNT_IF: *bytes = count_if_scratch_bytes(n); return 0;
+        case HPXHIP_ALGO_MINMAX_ELEMENT: *bytes = minmax_element_scratch_bytes(n); return 0;
         default: return HPXHIP_ERROR_INVALID_ARGUMENT;
     }
 }

@@ -2,3 +2,9 @@
 #pragma once
 #include <hpx/parallel/algorithms.hpp>
 #include <hpx/include/parallel_unique.hpp>
+#include <hpx/include/parallel_all_any_none.hpp>
+#include <hpx/include/parallel_count.hpp>
+#include <hpx/include/parallel_equal.hpp>
+#include <hpx/include/parallel_find.hpp>
+#include <hpx/include/parallel_minmax.hpp>
+#include <hpx/include/parallel_mismatch.hpp>

@@ -24,6 +24,13 @@
 //   remove, remove_if            remove.hpp:290, 367          -> Iter
 //   unique_copy                  unique.hpp:612               -> tagged_pair<in, out>
 //   unique                       unique.hpp:311               -> Iter
+//   find, find_if, find_if_not   find.hpp:70, 216, 382        -> Iter
+//   all_of, any_of, none_of      all_any_none.hpp             -> bool
+//   count, count_if              count.hpp:259, 451           -> difference_type
+//   min_element, max_element     minmax.hpp:46-66, 277        -> Iter
+//   minmax_element               minmax.hpp:513-541           -> pair<Iter, Iter>
+//   equal                        equal.hpp:229, 398           -> bool
+//   mismatch                     mismatch.hpp:227, 396        -> pair<Iter1, Iter2>
 //
 // Synchronous policies (seq, par, par_unseq) return the value after the
 // target's stream is synchronised (the reference's bulk_sync_execute,
@@ -640,6 +647,263 @@ detail::result_t<P, It> unique(P&& p, It first, It last, Pred&& pred = Pred(), P
         std::memcpy(&c, b, 8);
         return first + static_cast<std::ptrdiff_t>(c);
     });
+}
+
+// ------------------------------------------------------------ search family
+// Questions asked of a range (hpxhip/kernels/search_kernel.hpp): every call
+// leaves one uint64 (two for minmax_element) in a result slot.  The mapped
+// predicates of copy_if (traits::pred), a value, std::less / std::greater and
+// std::equal_to run the library's kernels; any other HPX_HOST_DEVICE
+// predicate, comparator or projection runs the same kernels as a device
+// closure (hipcc).
+namespace search {
+template <typename R, typename P, typename Fn>
+detail::result_t<P, R> index_result(P const& p, detail::hip::target const& t, detail::hip::result_slot slot,
+                                    char const* what, Fn fn) {
+    detail::fetch_slot(t, slot, 8, what);
+    return detail::finish_slot<R>(p, t, std::move(slot), [fn](unsigned char const* b) -> R {
+        uint64_t i;
+        std::memcpy(&i, b, 8);
+        return fn(i);
+    });
+}
+
+// the find_if call over [first, last): the slot that receives the index
+template <typename P, typename It, typename F>
+auto find_call(char const* what, P const& p, detail::hip::target const& t, It first, uint64_t n, F const& f,
+               bool negate) {
+    static_assert(detail::is_dev<It>, "find / all_of / any_of / none_of: device iterators required");
+    using T = detail::value_t<It>;
+    auto slot = t.make_result_slot();
+    T const* in = static_cast<T const*>(first.device_ptr());
+    uint64_t* index_dev = static_cast<uint64_t*>(slot.device());
+    if constexpr (detail::is_complete_pred<F>) {
+        using Tr = detail::tr::pred_t<F>;
+        T arg = static_cast<T>(Tr::arg(f));
+        detail::check(hpxhip_find_if(detail::dt<T>, Tr::kind, &arg, negate ? 1 : 0, in, n, index_dev, t.stream()),
+                      what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::find_if(t, in, n, f, negate, index_dev);
+#else
+        detail::no_device_mapping<F>(what);
+#endif
+    }
+    return slot;
+}
+
+template <typename P, typename It, typename F>
+detail::result_t<P, It> find_iter(char const* what, P const& p, It first, It last, F const& f, bool negate) {
+    auto const& t = detail::target_of(p, first);
+    auto slot = find_call(what, p, t, first, detail::distance(first, last), f, negate);
+    return index_result<It>(p, t, std::move(slot), what,
+                            [first](uint64_t i) { return first + static_cast<std::ptrdiff_t>(i); });
+}
+
+// found: the value when the index is below n
+template <typename P, typename It, typename F>
+detail::result_t<P, bool> find_bool(char const* what, P const& p, It first, It last, F const& f, bool negate,
+                                    bool found) {
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last);
+    auto slot = find_call(what, p, t, first, n, f, negate);
+    return index_result<bool>(p, t, std::move(slot), what, [n, found](uint64_t i) { return (i < n) == found; });
+}
+
+template <typename Comp, typename Proj>
+constexpr bool is_mapped_compare = detail::is_complete_compare<Comp> &&
+                                   std::is_same<std::decay_t<Proj>, util::projection_identity>::value;
+
+template <int WHICH, typename P, typename It, typename Comp, typename Proj>
+auto extreme_call(char const* what, P const& p, detail::hip::target const& t, It first, It last, Comp const& comp,
+                  Proj const& proj) {
+    static_assert(detail::is_dev<It>, "min_element / max_element / minmax_element: device iterators required");
+    using T = detail::value_t<It>;
+    auto slot = t.make_result_slot();
+    T const* in = static_cast<T const*>(first.device_ptr());
+    const uint64_t n = detail::distance(first, last);
+    uint64_t* out = static_cast<uint64_t*>(slot.device());
+    if constexpr (is_mapped_compare<Comp, Proj>) {
+        detail::check(hpxhip_minmax_element(detail::dt<T>, WHICH, detail::tr::compare_t<Comp>::descending ? 1 : 0, in,
+                                            n, out, t.stream(), nullptr, 0),
+                      what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::arg_extreme<WHICH>(t, in, n, comp, proj, out);
+#else
+        detail::no_device_mapping<Comp>(what);
+#endif
+    }
+    return slot;
+}
+
+template <typename P, typename It1, typename It2, typename Pred>
+auto mismatch_call(char const* what, P const& p, detail::hip::target const& t, It1 first1, It2 first2, uint64_t n,
+                   Pred const& pred) {
+    static_assert(detail::is_dev<It1> && detail::is_dev<It2>, "equal / mismatch: device iterators required");
+    using T = detail::value_t<It1>;
+    static_assert(std::is_same<T, detail::value_t<It2>>::value, "equal / mismatch: both ranges hold one value type");
+    auto slot = t.make_result_slot();
+    T const* a = static_cast<T const*>(first1.device_ptr());
+    T const* b = static_cast<T const*>(first2.device_ptr());
+    uint64_t* index_dev = static_cast<uint64_t*>(slot.device());
+    using D = std::decay_t<Pred>;
+    if constexpr (std::is_same<D, std::equal_to<>>::value || std::is_same<D, std::equal_to<T>>::value) {
+        detail::check(hpxhip_mismatch(detail::dt<T>, a, b, n, index_dev, t.stream()), what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::mismatch(t, a, b, n, pred, index_dev);
+#else
+        detail::no_device_mapping<Pred>(what);
+#endif
+    }
+    return slot;
+}
+}  // namespace search
+
+// find.hpp:216 / :382 / :70: the first iterator whose element satisfies f
+// (does not satisfy f; equals value), or last.  Blocks above a hit that is
+// already known skip their loads; the result is exact.
+template <typename P, typename It, typename F>
+detail::result_t<P, It> find_if(P&& p, It first, It last, F&& f) {
+    return search::find_iter("find_if", p, first, last, f, false);
+}
+template <typename P, typename It, typename F>
+detail::result_t<P, It> find_if_not(P&& p, It first, It last, F&& f) {
+    return search::find_iter("find_if_not", p, first, last, f, true);
+}
+template <typename P, typename It, typename V>
+detail::result_t<P, It> find(P&& p, It first, It last, V const& value) {
+    using T = detail::value_t<It>;
+    return search::find_iter("find", p, first, last, compute::hip::functional::equal_to<T>{static_cast<T>(value)},
+                             false);
+}
+
+// all_any_none.hpp: any_of = find_if found something (false when empty),
+// none_of = its negation, all_of = find_if_not found nothing (true when empty).
+template <typename P, typename It, typename F>
+detail::result_t<P, bool> any_of(P&& p, It first, It last, F&& f) {
+    return search::find_bool("any_of", p, first, last, f, false, true);
+}
+template <typename P, typename It, typename F>
+detail::result_t<P, bool> none_of(P&& p, It first, It last, F&& f) {
+    return search::find_bool("none_of", p, first, last, f, false, false);
+}
+template <typename P, typename It, typename F>
+detail::result_t<P, bool> all_of(P&& p, It first, It last, F&& f) {
+    return search::find_bool("all_of", p, first, last, f, true, false);
+}
+
+// count.hpp:451 / :259: the reduce kernel over `f(x) ? 1 : 0`.
+template <typename P, typename It, typename F>
+detail::result_t<P, typename std::iterator_traits<It>::difference_type> count_if(P&& p, It first, It last, F&& f) {
+    static_assert(detail::is_dev<It>, "count / count_if: device iterators required");
+    using T = detail::value_t<It>;
+    using D = typename std::iterator_traits<It>::difference_type;
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last);
+    auto slot = t.make_result_slot();
+    T const* in = static_cast<T const*>(first.device_ptr());
+    uint64_t* count_dev = static_cast<uint64_t*>(slot.device());
+    if constexpr (detail::is_complete_pred<F>) {
+        using Tr = detail::tr::pred_t<F>;
+        T arg = static_cast<T>(Tr::arg(f));
+        detail::check(hpxhip_count_if(detail::dt<T>, Tr::kind, &arg, in, n, count_dev, t.stream(), nullptr, 0),
+                      "count_if");
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::count_if(t, in, n, f, count_dev);
+#else
+        detail::no_device_mapping<F>("count_if");
+#endif
+    }
+    return search::index_result<D>(p, t, std::move(slot), "count_if", [](uint64_t c) { return static_cast<D>(c); });
+}
+template <typename P, typename It, typename V>
+detail::result_t<P, typename std::iterator_traits<It>::difference_type> count(P&& p, It first, It last,
+                                                                              V const& value) {
+    using T = detail::value_t<It>;
+    return count_if(std::forward<P>(p), first, last, compute::hip::functional::equal_to<T>{static_cast<T>(value)});
+}
+
+// minmax.hpp:46-66 / :277 / :513-541 (f = less, proj = identity): the FIRST
+// smallest, the FIRST largest, and for minmax_element the FIRST smallest and
+// the LAST largest in one pass; first for an empty range.  With NaNs under
+// std::less the result is some valid iterator into the range, the same one
+// run to run (search_kernel.hpp).
+template <typename P, typename It, typename Comp = std::less<>, typename Proj = util::projection_identity>
+detail::result_t<P, It> min_element(P&& p, It first, It last, Comp&& comp = Comp(), Proj&& proj = Proj()) {
+    auto const& t = detail::target_of(p, first);
+    auto slot = search::extreme_call<HPXHIP_X_MIN>("min_element", p, t, first, last, comp, proj);
+    return search::index_result<It>(p, t, std::move(slot), "min_element",
+                                    [first](uint64_t i) { return first + static_cast<std::ptrdiff_t>(i); });
+}
+template <typename P, typename It, typename Comp = std::less<>, typename Proj = util::projection_identity>
+detail::result_t<P, It> max_element(P&& p, It first, It last, Comp&& comp = Comp(), Proj&& proj = Proj()) {
+    auto const& t = detail::target_of(p, first);
+    auto slot = search::extreme_call<HPXHIP_X_MAX>("max_element", p, t, first, last, comp, proj);
+    return search::index_result<It>(p, t, std::move(slot), "max_element",
+                                    [first](uint64_t i) { return first + static_cast<std::ptrdiff_t>(i); });
+}
+template <typename P, typename It, typename Comp = std::less<>, typename Proj = util::projection_identity>
+detail::result_t<P, std::pair<It, It>> minmax_element(P&& p, It first, It last, Comp&& comp = Comp(),
+                                                      Proj&& proj = Proj()) {
+    using R = std::pair<It, It>;
+    auto const& t = detail::target_of(p, first);
+    auto slot = search::extreme_call<HPXHIP_X_MINMAX>("minmax_element", p, t, first, last, comp, proj);
+    detail::fetch_slot(t, slot, 16, "minmax_element");
+    return detail::finish_slot<R>(p, t, std::move(slot), [first](unsigned char const* b) {
+        uint64_t i[2];
+        std::memcpy(i, b, 16);
+        return R{first + static_cast<std::ptrdiff_t>(i[0]), first + static_cast<std::ptrdiff_t>(i[1])};
+    });
+}
+
+// mismatch.hpp:227 (three iterators) / :396 (four: over min(n1, n2)) ->
+// pair<It1, It2>, the first position with !pred(a, b) (std::equal_to: by
+// value, a NaN differs from itself), or the ends of what was searched.
+template <typename P, typename It1, typename It2, typename Pred = std::equal_to<>,
+          typename = std::enable_if_t<!detail::is_dev<Pred>>>
+detail::result_t<P, std::pair<It1, It2>> mismatch(P&& p, It1 first1, It1 last1, It2 first2, Pred&& pred = Pred()) {
+    using R = std::pair<It1, It2>;
+    auto const& t = detail::target_of(p, first1);
+    auto slot = search::mismatch_call("mismatch", p, t, first1, first2, detail::distance(first1, last1), pred);
+    return search::index_result<R>(p, t, std::move(slot), "mismatch", [first1, first2](uint64_t i) {
+        return R{first1 + static_cast<std::ptrdiff_t>(i), first2 + static_cast<std::ptrdiff_t>(i)};
+    });
+}
+template <typename P, typename It1, typename It2, typename Pred = std::equal_to<>>
+detail::result_t<P, std::pair<It1, It2>> mismatch(P&& p, It1 first1, It1 last1, It2 first2, It2 last2,
+                                                  Pred&& pred = Pred()) {
+    using R = std::pair<It1, It2>;
+    auto const& t = detail::target_of(p, first1);
+    const uint64_t n = std::min(detail::distance(first1, last1), detail::distance(first2, last2));
+    auto slot = search::mismatch_call("mismatch", p, t, first1, first2, n, pred);
+    return search::index_result<R>(p, t, std::move(slot), "mismatch", [first1, first2](uint64_t i) {
+        return R{first1 + static_cast<std::ptrdiff_t>(i), first2 + static_cast<std::ptrdiff_t>(i)};
+    });
+}
+
+// equal.hpp:229 / :398: mismatch found nothing; with four iterators ranges of
+// different length are unequal without a launch.
+template <typename P, typename It1, typename It2, typename Pred = std::equal_to<>,
+          typename = std::enable_if_t<!detail::is_dev<Pred>>>
+detail::result_t<P, bool> equal(P&& p, It1 first1, It1 last1, It2 first2, Pred&& pred = Pred()) {
+    auto const& t = detail::target_of(p, first1);
+    const uint64_t n = detail::distance(first1, last1);
+    auto slot = search::mismatch_call("equal", p, t, first1, first2, n, pred);
+    return search::index_result<bool>(p, t, std::move(slot), "equal", [n](uint64_t i) { return i == n; });
+}
+template <typename P, typename It1, typename It2, typename Pred = std::equal_to<>>
+detail::result_t<P, bool> equal(P&& p, It1 first1, It1 last1, It2 first2, It2 last2, Pred&& pred = Pred()) {
+    auto const& t = detail::target_of(p, first1);
+    const uint64_t n = detail::distance(first1, last1);
+    if (n != detail::distance(first2, last2)) {
+        static_assert(detail::is_dev<It1> && detail::is_dev<It2>, "equal: device iterators required");
+        return detail::finish<bool>(p, t, [] { return false; });
+    }
+    auto slot = search::mismatch_call("equal", p, t, first1, first2, n, pred);
+    return search::index_result<bool>(p, t, std::move(slot), "equal", [n](uint64_t i) { return i == n; });
 }
 
 // ------------------------------------------------------------- transform
@@ -1473,6 +1737,19 @@ HPXHIP_GUARDED_ALGORITHM(remove_if)
 HPXHIP_GUARDED_ALGORITHM(remove)
 HPXHIP_GUARDED_ALGORITHM(unique_copy)
 HPXHIP_GUARDED_ALGORITHM(unique)
+HPXHIP_GUARDED_ALGORITHM(find)
+HPXHIP_GUARDED_ALGORITHM(find_if)
+HPXHIP_GUARDED_ALGORITHM(find_if_not)
+HPXHIP_GUARDED_ALGORITHM(all_of)
+HPXHIP_GUARDED_ALGORITHM(any_of)
+HPXHIP_GUARDED_ALGORITHM(none_of)
+HPXHIP_GUARDED_ALGORITHM(count)
+HPXHIP_GUARDED_ALGORITHM(count_if)
+HPXHIP_GUARDED_ALGORITHM(min_element)
+HPXHIP_GUARDED_ALGORITHM(max_element)
+HPXHIP_GUARDED_ALGORITHM(minmax_element)
+HPXHIP_GUARDED_ALGORITHM(equal)
+HPXHIP_GUARDED_ALGORITHM(mismatch)
 HPXHIP_GUARDED_ALGORITHM(transform)
 HPXHIP_GUARDED_ALGORITHM(reduce)
 HPXHIP_GUARDED_ALGORITHM(transform_reduce)
@@ -1529,6 +1806,19 @@ using parallel::v1::remove_copy_if;
 using parallel::v1::remove_if;
 using parallel::v1::stable_partition;
 using parallel::v1::is_sorted;
+using parallel::v1::all_of;
+using parallel::v1::any_of;
+using parallel::v1::none_of;
+using parallel::v1::count;
+using parallel::v1::count_if;
+using parallel::v1::equal;
+using parallel::v1::find;
+using parallel::v1::find_if;
+using parallel::v1::find_if_not;
+using parallel::v1::max_element;
+using parallel::v1::min_element;
+using parallel::v1::minmax_element;
+using parallel::v1::mismatch;
 using parallel::v1::sort;
 using parallel::v1::sort_by_key;
 using parallel::v1::transform;

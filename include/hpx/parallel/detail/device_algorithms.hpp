@@ -18,6 +18,11 @@
 //                              compaction_kernel.hpp (ballot ranks, look-back;
 //                                                   one- and two-sided)
 //   reduce_by_key              reduce_by_key_kernel.hpp (segmented look-back)
+//   find_if, find_if_not, all_of, any_of, none_of, equal, mismatch, count_if,
+//   min_element, max_element, minmax_element
+//                              search_kernel.hpp   (first hit by atomic min with
+//                                                   an early-exit hint; arg-extreme
+//                                                   pairs; count on the reduce kernel)
 //   sort (comp, proj)          merge_kernel.hpp    (block sort in LDS, then
 //                                                   merge-path passes)
 //
@@ -49,6 +54,7 @@
 #include <hpxhip/kernels/reduce_by_key_kernel.hpp>
 #include <hpxhip/kernels/reduce_kernel.hpp>
 #include <hpxhip/kernels/scan_kernel.hpp>
+#include <hpxhip/kernels/search_kernel.hpp>
 #endif
 
 namespace hpx { namespace parallel { inline namespace v1 { namespace detail {
@@ -418,6 +424,69 @@ void merge_sort(compute::hip::target const& t, T* data, uint64_t n, Comp const& 
         std::swap(src, dst);
     }
     if (src != data) compute::hip::detail::check(hpxhip_memcpy_async(data, src, n * sizeof(T), HPXHIP_D2D, t.stream()), "sort copy-back");
+}
+// ------------------------------------------------------------ search family
+// find.hpp, all_any_none.hpp, count.hpp, minmax.hpp, equal.hpp, mismatch.hpp
+// with any predicate, comparator and projection: the library's kernels
+// (search_kernel.hpp) through the library's launchers, instantiated for the
+// callable.  Every result is a uint64 in a result slot.
+template <typename T, typename Pred>
+struct find_source {
+    const T* a;
+    const T* b;
+    Pred pred;
+    bool negate;
+    __device__ __forceinline__ bool hit(T x) const { return static_cast<bool>(pred(x)) != negate; }
+};
+template <typename T, typename Pred>
+struct mismatch_source {
+    const T* a;
+    const T* b;
+    Pred pred;
+    __device__ __forceinline__ bool hit(T x, T y) const { return !static_cast<bool>(pred(x, y)); }
+};
+
+inline void search_launched(hipError_t e, char const* what) {
+    if (e != hipSuccess)
+        throw hpx::kernel_error(static_cast<int>(e), std::string(what) + " (device closure): " + hipGetErrorString(e));
+}
+
+// *index_dev <- the smallest i with pred(in[i]) != negate, else n
+template <typename T, typename Pred>
+void find_if(compute::hip::target const& t, T const* in, uint64_t n, Pred const& pred, bool negate,
+             uint64_t* index_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "find (device closure): 4- or 8-byte element types");
+    using S = find_source<T, std::decay_t<Pred>>;
+    search_launched(K::search_detail::launch_find<T, S, false>(S{in, nullptr, pred, negate}, n, index_dev, stream_of(t)),
+                    "find_if");
+}
+
+// *index_dev <- the smallest i with !pred(a[i], b[i]), else n
+template <typename T, typename Pred>
+void mismatch(compute::hip::target const& t, T const* a, T const* b, uint64_t n, Pred const& pred,
+              uint64_t* index_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "mismatch (device closure): 4- or 8-byte element types");
+    using S = mismatch_source<T, std::decay_t<Pred>>;
+    search_launched(K::search_detail::launch_find<T, S, true>(S{a, b, pred}, n, index_dev, stream_of(t)), "mismatch");
+}
+
+template <typename T, typename Pred>
+void count_if(compute::hip::target const& t, T const* in, uint64_t n, Pred const& pred, uint64_t* count_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "count_if (device closure): 4- or 8-byte element types");
+    void* ws = n ? scratch(t, K::reduce_detail::max_blocks(n) * sizeof(uint64_t), "count_if scratch") : nullptr;
+    using P = as_bool_pred<T, std::decay_t<Pred>>;
+    search_launched(K::search_detail::launch_count<T>(in, n, P{pred}, count_dev, ws, stream_of(t)), "count_if");
+}
+
+// WHICH: HPXHIP_X_MIN / MAX / MINMAX; out: one index (two for MINMAX)
+template <int WHICH, typename T, typename Comp, typename Proj>
+void arg_extreme(compute::hip::target const& t, T const* in, uint64_t n, Comp const& comp, Proj const& proj,
+                 uint64_t* out) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "min/max_element (device closure): 4- or 8-byte element types");
+    void* ws = n ? scratch(t, K::search_detail::arg_scratch_bytes(n), "minmax_element scratch") : nullptr;
+    using L = projected_less<T, std::decay_t<Comp>, std::decay_t<Proj>>;
+    search_launched(K::search_detail::launch_arg<T, L, WHICH>(in, n, L{comp, proj}, out, ws, stream_of(t)),
+                    "minmax_element");
 }
 #endif  // HPX_HAVE_HIP_DEVICE_CLOSURES
 

@@ -28,6 +28,8 @@
  *   - inclusive/exclusive_scan  -> inclusive_scan.hpp:90-173,
  *       exclusive_scan.hpp:100-175 + util/scan_partitioner.hpp:62-156
  *   - copy_if                   -> copy.hpp:401-494
+ *   - find / count / min_element / equal / mismatch -> find.hpp:70-382,
+ *       count.hpp:259,451, minmax.hpp:46-541, equal.hpp:229, mismatch.hpp:227
  *   - sort / sort_by_key        -> sort.hpp:182-276, sort_by_key.hpp:42-78
  *   - 1d_stencil heat step      -> examples/1d_stencil/1d_stencil_1.cpp:41-72,
  *       1d_stencil_4_parallel.cpp:87-118
@@ -140,7 +142,10 @@ enum hpxhip_algo {
     HPXHIP_ALGO_REDUCE_BY_KEY = 7, /* dtype = the key dtype, aux_dtype = the value dtype */
     HPXHIP_ALGO_PARTITION_COPY = 8,
     HPXHIP_ALGO_STABLE_PARTITION = 9, /* the tile state plus n elements */
-    HPXHIP_ALGO_UNIQUE_COPY = 10
+    HPXHIP_ALGO_UNIQUE_COPY = 10,
+    /* 11 is not assigned */
+    HPXHIP_ALGO_COUNT_IF = 12,
+    HPXHIP_ALGO_MINMAX_ELEMENT = 13 /* the size for HPXHIP_X_MINMAX, enough for each `which` */
 };
 
 typedef struct hpxhip_stream_opaque* hpxhip_stream; /* == hipStream_t */
@@ -405,6 +410,51 @@ int hpxhip_stable_partition(int dtype, int pred_kind, const void* pred_arg, void
 int hpxhip_unique_copy(int dtype, int rel_kind, const void* rel_arg, const void* in, void* out,
                        uint64_t n, uint64_t* count_dev, hpxhip_stream stream,
                        void* scratch, size_t scratch_bytes);
+
+/* ------------------------------------------------------ search family */
+/* Questions asked of a range; every result is one device uint64 (two for
+   HPXHIP_X_MINMAX), read back by the caller as copy_if's count is.  Each call
+   reads every byte at most once, at the geometry of hpxhip_transform_reduce,
+   and writes nothing but its result.  Predicates are the hpxhip_pred kinds
+   with copy_if's meaning (a NaN fails P_LT, so negate = 1 finds it).
+   INVALID_ARGUMENT: a null result pointer, a null input with n > 0, a pointer
+   not aligned to its element (the result: 8 bytes), an unknown pred_kind /
+   which, scratch too small.  UNSUPPORTED: P_BITS on F32 / F64. */
+
+/* find.hpp:70,216,382 (find, find_if, find_if_not) and all_any_none.hpp:
+   *index_dev = the smallest i in [0, n) with pred(in[i]) != (negate != 0),
+   or n if there is none (n == 0 writes 0).  Blocks whose whole chunk lies
+   above a hit that is already known skip their loads, so a hit near the
+   front does not cost a pass over the range (the reference's
+   util::cancellation_token); the result is exact whatever order blocks run
+   in.  find(value) is P_EQ, find_if_not is negate = 1, any_of is
+   `*index_dev != n`, all_of is `*index_dev == n` with negate = 1. */
+int hpxhip_find_if(int dtype, int pred_kind, const void* pred_arg, int negate, const void* in,
+                   uint64_t n, uint64_t* index_dev, hpxhip_stream stream);
+/* mismatch.hpp:227,396 and equal.hpp:229,398: *index_dev = the smallest i in [0, n)
+   with !(in1[i] == in2[i]) by value (-0.0 == +0.0; a NaN differs from
+   itself), or n if the ranges are equal (n == 0 writes 0).  The same early
+   exit.  in1 and in2 may be misaligned to each other (element loads). */
+int hpxhip_mismatch(int dtype, const void* in1, const void* in2, uint64_t n, uint64_t* index_dev,
+                    hpxhip_stream stream);
+/* count.hpp:259,451: *count_dev = the number of i with pred(in[i]) -- the
+   transform_reduce kernel over `pred(x) ? 1 : 0`.  count(value) is P_EQ (a
+   NaN is never counted, 0.0 counts -0.0).  Scratch: HPXHIP_ALGO_COUNT_IF. */
+int hpxhip_count_if(int dtype, int pred_kind, const void* pred_arg, const void* in, uint64_t n,
+                    uint64_t* count_dev, hpxhip_stream stream, void* scratch, size_t scratch_bytes);
+/* minmax.hpp:46-66 (min_element: the FIRST smallest), :277 (max_element: the
+   FIRST largest), :513-541 (minmax_element: the FIRST smallest and the LAST
+   largest, one pass), under std::less, or std::greater if descending != 0
+   (then "smallest" is the largest value).  index_dev: one index (two for
+   HPXHIP_X_MINMAX: min, then max); n == 0 writes 0 to each.  Floats compare by
+   value, -0.0 and +0.0 tie.  With NaNs in the range the comparison is no
+   strict weak order and the result is unspecified as in the standard: here it
+   is a valid index in [0, n), bitwise reproducible run to run.
+   Scratch: HPXHIP_ALGO_MINMAX_ELEMENT. */
+enum hpxhip_extreme { HPXHIP_X_MIN = 0, HPXHIP_X_MAX = 1, HPXHIP_X_MINMAX = 2 };
+int hpxhip_minmax_element(int dtype, int which, int descending, const void* in, uint64_t n,
+                          uint64_t* index_dev /* 1 word; 2 for MINMAX */, hpxhip_stream stream,
+                          void* scratch, size_t scratch_bytes);
 
 /* ------------------------------------------------------ reduce_by_key */
 /* reduce_by_key.hpp:586: a run is a maximal range of consecutive equal keys

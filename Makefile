@@ -56,7 +56,8 @@ define mw_spill_guard
 	@awk '/Function Name:/ {k = ($$0 ~ /k_mw_merge/)} k && /SGPRs Spill: [1-9]/ {bad = 1; print} \
 	     END {if (bad) {print "merge.hip: k_mw_merge spills SGPRs (see Makefile)"; exit 1}}' $(1)
 endef
-$(BUILD)/csrc/merge.o: hpx_amd/csrc/merge.hip $(KHDR)
+# set.hip (the set operations) is part of merge.hip's translation unit
+$(BUILD)/csrc/merge.o: hpx_amd/csrc/merge.hip hpx_amd/csrc/set.hip $(KHDR)
 	@mkdir -p $(dir $@)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o $@ 2> $(BUILD)/csrc/merge.usage || \
 	    (cat $(BUILD)/csrc/merge.usage; rm -f $@; exit 1)
@@ -70,7 +71,7 @@ MWVAR    := mw512 mwminw4
 MWVAR_mw512   := -DHPXHIP_MW_THREADS=512 -DHPXHIP_MW_MINW=4
 MWVAR_mwminw4 := -DHPXHIP_MW_MINW=4
 mw-variants: $(MWVAR:%=hpx_amd/variants/%/libhpxhip.so)
-hpx_amd/variants/%/libhpxhip.so: hpx_amd/csrc/merge.hip $(filter-out $(BUILD)/csrc/merge.o,$(KOBJ)) $(KHDR)
+hpx_amd/variants/%/libhpxhip.so: hpx_amd/csrc/merge.hip hpx_amd/csrc/set.hip $(filter-out $(BUILD)/csrc/merge.o,$(KOBJ)) $(KHDR)
 	@mkdir -p $(dir $@) $(BUILD)/variants/$*
 	$(HIPCC) $(HIPFLAGS) $(MWVAR_$*) -Rpass-analysis=kernel-resource-usage -c $< -o $(BUILD)/variants/$*/merge.o \
 	    2> $(BUILD)/variants/$*/merge.usage || (cat $(BUILD)/variants/$*/merge.usage; exit 1)
@@ -103,7 +104,7 @@ tests/cxx/bin/oracle_sanitize: tests/cxx/oracle_sanitize.cpp oracle/oracle.cpp o
 
 # ... and the hipcc-compiled ones (device closures, HPX_HOST_DEVICE lambdas)
 HIPT     := device_closures partitioned_vector closure_algorithms closure_timing dataflow_stencil bench_targets \
-            reduce_by_key partition unique search
+            reduce_by_key partition unique search set_operations
 HIPTBIN  := $(HIPT:%=tests/cxx/bin/%)
 HTFLAGS  := -O2 -std=c++17 --offload-arch=$(ARCH) --offload-compress -Wall -Wno-unused-parameter -Iinclude
 

@@ -30,7 +30,8 @@ H2H, H2D, D2H, D2D, DEFAULT = range(5)
 GEN_IOTA, GEN_BITS, GEN_RANGE, GEN_UNIT = range(4)
 (ALGO_REDUCE, ALGO_SCAN, ALGO_COPY_IF, ALGO_SORT, ALGO_SORT_BY_KEY, ALGO_MERGE, ALGO_MERGE_RUNS,
  ALGO_REDUCE_BY_KEY, ALGO_PARTITION_COPY, ALGO_STABLE_PARTITION, ALGO_UNIQUE_COPY) = range(11)
-ALGO_COUNT_IF, ALGO_MINMAX_ELEMENT = 12, 13  # 11 is not assigned
+ALGO_COUNT_IF, ALGO_MINMAX_ELEMENT, ALGO_SET_OPERATION = 12, 13, 14  # 11 is not assigned
+SET_UNION, SET_INTERSECTION, SET_DIFFERENCE, SET_SYMMETRIC_DIFFERENCE = range(4)
 STENCIL_MAX_FUSED = 16  # HPXHIP_STENCIL_MAX_FUSED
 
 SUCCESS = 0
@@ -174,6 +175,7 @@ SIGNATURES = {
     "hpxhip_sort": [_i, _vp, _u64, _i, _vp, _vp, _sz],
     "hpxhip_sort_by_key": [_i, _i, _vp, _vp, _u64, _i, _vp, _vp, _sz],
     "hpxhip_merge": [_i, _vp, _u64, _vp, _u64, _vp, _i, _vp, _vp, _sz],
+    "hpxhip_set_operation": [_i, _i, _vp, _u64, _vp, _u64, _vp, _i, _vp, _vp, _vp, _sz],
     "hpxhip_merge_runs": [_i, _vp, _vp, _i, _vp, _i, _vp, _vp, _sz],
     "hpxhip_unsorted_pairs": [_i, _vp, _u64, _i, _vp, _vp],
     "hpxhip_sorted_bounds": [_i, _vp, _u64, _vp, _u64, _i, _i, _vp, _vp],

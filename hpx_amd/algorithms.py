@@ -25,6 +25,14 @@ calls one whole-algorithm entry point of the C ABI (include/hpxhip.h):
   remove(_if)                remove.hpp:290, 367
   unique / unique_copy       unique.hpp:311, 612 (one pass instead of the
                              reference's three)
+  set_union                  set_union.hpp:47
+  set_intersection           set_intersection.hpp
+  set_difference             set_difference.hpp
+  set_symmetric_difference   set_symmetric_difference.hpp
+  includes                   includes.hpp:129 (all five: one pass instead of
+                             the reference's chunked std::set_* into a len1 +
+                             len2 buffer and a second copy,
+                             detail/set_operation.hpp:72-193)
   find / find_if(_not)       find.hpp:70, 216, 382 (early exit: a hint on the
   all_of / any_of / none_of  result word, all_any_none.hpp)
   count / count_if           count.hpp:259, 451
@@ -768,6 +776,94 @@ def merge(pol, first1, last1, first2, last2, dest, comp=F.less):
     return _finish(is_task, stream, tgt, lambda: (last1, last2, dest + (n1 + n2)))
 
 
+# ------------------------------------------------------------ set operations
+def _set_call(what, op, pol, first1, last1, first2, last2, dest, comp, count_only=False):
+    """One hpxhip_set_operation call -> (stream, tgt, is_task, count thunk).
+    Every argument check comes before the first device call."""
+    _exec_of(pol)
+    comp = F.require(comp, F.Compare, what)
+    n1 = _check_range(first1, last1)
+    n2 = _check_range(first2, last2)
+    if first1.dtype != first2.dtype:
+        raise TypeError(f"{what}: the ranges must have one dtype")
+    iters = [first1, first2]
+    if not count_only:
+        if not isinstance(dest, iterator):
+            raise TypeError(f"{what}: dest must be a device iterator")
+        if dest.dtype != first1.dtype:
+            raise TypeError(f"{what}: the ranges and dest must have one dtype")
+        iters.append(dest)
+    stream, tgt, is_task = _context(pol, *iters)
+    dev, host = _slots_for(tgt).next()
+    L.call("hpxhip_set_operation", first1.dtype, op, _vp(first1.address), n1, _vp(first2.address), n2,
+           None if count_only else _vp(dest.address), 1 if comp.descending else 0, _vp(dev), stream, None, 0)
+    L.call("hpxhip_memcpy_async", _vp(host), _vp(dev), 8, L.D2H, stream)
+    return stream, tgt, is_task, lambda: _read_host(host, L.U64)
+
+
+def set_union(pol, first1, last1, first2, last2, dest, comp=F.less):
+    """set_union.hpp:47 (std::set_union on multisets): every element of
+    [first1, last1), and of a value with cnt1 / cnt2 equivalent elements in
+    the two ranges the last max(cnt2 - cnt1, 0) of [first2, last2), to dest
+    in the order of the stable merge (range 1 first on ties); returns
+    dest + count, or its future under par(task).  Both ranges must be sorted
+    under comp (F.less / F.greater), which is the key order of sort and merge:
+    integers as std::less, floats in IEEE total order -- -0.0 and +0.0 are
+    different keys, two NaNs with the same bits are the same key -- so
+    sorting and then applying a set operation agree on every dtype.  dest
+    must not overlap either input."""
+    stream, tgt, is_task, count = _set_call("set_union", L.SET_UNION, pol, first1, last1, first2, last2, dest, comp)
+    return _finish(is_task, stream, tgt, lambda: dest + count())
+
+
+def set_intersection(pol, first1, last1, first2, last2, dest, comp=F.less):
+    """set_intersection.hpp (std::set_intersection on multisets): of a value
+    with cnt1 / cnt2 equivalent elements the first min(cnt1, cnt2) of
+    [first1, last1), to dest in order; returns dest + count, or its future
+    under par(task).  Key order (floats: IEEE total order, -0.0 != +0.0,
+    equal-bit NaNs match) and aliasing as for set_union."""
+    stream, tgt, is_task, count = _set_call("set_intersection", L.SET_INTERSECTION, pol, first1, last1, first2,
+                                            last2, dest, comp)
+    return _finish(is_task, stream, tgt, lambda: dest + count())
+
+
+def set_difference(pol, first1, last1, first2, last2, dest, comp=F.less):
+    """set_difference.hpp (std::set_difference on multisets): of a value with
+    cnt1 / cnt2 equivalent elements the last max(cnt1 - cnt2, 0) of
+    [first1, last1), to dest in order; returns dest + count, or its future
+    under par(task).  Key order (floats: IEEE total order, -0.0 != +0.0,
+    equal-bit NaNs match) and aliasing as for set_union."""
+    stream, tgt, is_task, count = _set_call("set_difference", L.SET_DIFFERENCE, pol, first1, last1, first2, last2,
+                                            dest, comp)
+    return _finish(is_task, stream, tgt, lambda: dest + count())
+
+
+def set_symmetric_difference(pol, first1, last1, first2, last2, dest, comp=F.less):
+    """set_symmetric_difference.hpp (std::set_symmetric_difference on
+    multisets): of a value with cnt1 / cnt2 equivalent elements the last
+    max(cnt1 - cnt2, 0) of [first1, last1) and the last max(cnt2 - cnt1, 0)
+    of [first2, last2), to dest in the order of the stable merge; returns
+    dest + count, or its future under par(task).  Key order (floats: IEEE
+    total order, -0.0 != +0.0, equal-bit NaNs match) and aliasing as for
+    set_union."""
+    stream, tgt, is_task, count = _set_call("set_symmetric_difference", L.SET_SYMMETRIC_DIFFERENCE, pol, first1,
+                                            last1, first2, last2, dest, comp)
+    return _finish(is_task, stream, tgt, lambda: dest + count())
+
+
+def includes(pol, first1, last1, first2, last2, comp=F.less):
+    """includes.hpp:129 (std::includes on multisets): True iff every value's
+    count in [first2, last2) is at most its count in [first1, last1) -- iff
+    set_difference(range 2, range 1) keeps nothing, which is how it is
+    counted (no output is written); an empty second range gives True; a
+    future under par(task).  Both ranges sorted under comp, in the key order
+    of set_union (floats: IEEE total order, -0.0 != +0.0, equal-bit NaNs
+    match).  The whole of both ranges is read (no early exit)."""
+    stream, tgt, is_task, count = _set_call("includes", L.SET_DIFFERENCE, pol, first2, last2, first1, last1, None,
+                                            comp, count_only=True)
+    return _finish(is_task, stream, tgt, lambda: count() == 0)
+
+
 # ------------------------------------------------------------------ for_loop
 class induction:
     """for_loop_induction.hpp:210-219: an induction variable whose value at
@@ -1056,7 +1152,9 @@ for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "c
               "unique", "find", "find_if", "find_if_not", "all_of", "any_of", "none_of", "count", "count_if",
               "min_element", "max_element", "minmax_element", "equal", "mismatch", "transform",
               "reduce", "transform_reduce", "inclusive_scan", "exclusive_scan", "transform_inclusive_scan",
-              "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge", "for_loop_n", "for_loop",
+              "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge",
+              "set_union", "set_intersection", "set_difference", "set_symmetric_difference", "includes", "for_loop_n",
+              "for_loop",
               "for_loop_n_strided", "for_loop_strided"):
     if _name in globals():
         globals()[_name] = _guarded(globals()[_name])

@@ -315,5 +315,6 @@ size_t reduce_by_key_scratch_bytes(int key_dtype, int value_dtype, uint64_t n);
 size_t sort_scratch_bytes(int key_dtype, int value_dtype, uint64_t n);
 size_t merge_scratch_bytes(uint64_t n);
 size_t merge_runs_scratch_bytes(uint64_t n);
+size_t set_operation_scratch_bytes(uint64_t n);
 
 }  // namespace hpxhip

@@ -656,3 +656,7 @@ int hpxhip_unsorted_pairs(int dtype, const void* keys, uint64_t n, int descendin
 }
 
 }  // extern "C"
+
+// The set operations on sorted ranges (set_union ... includes): the merge
+// tile with a keep rule, in this translation unit.
+#include "set.hip"

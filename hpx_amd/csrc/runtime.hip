@@ -534,6 +534,7 @@ int hpxhip_scratch_bytes(int algo, int dtype, int aux_dtype, uint64_t n, size_t*
         case HPXHIP_ALGO_UNIQUE_COPY: *bytes = unique_scratch_bytes(dtype, n); return 0;
         case HPXHIP_ALGO_COUNT_IF: *bytes = count_if_scratch_bytes(n); return 0;
         case HPXHIP_ALGO_MINMAX_ELEMENT: *bytes = minmax_element_scratch_bytes(n); return 0;
+        case HPXHIP_ALGO_SET_OPERATION: *bytes = set_operation_scratch_bytes(n); return 0;
         default: return HPXHIP_ERROR_INVALID_ARGUMENT;
     }
 }

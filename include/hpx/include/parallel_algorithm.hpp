@@ -8,3 +8,4 @@
 #include <hpx/include/parallel_find.hpp>
 #include <hpx/include/parallel_minmax.hpp>
 #include <hpx/include/parallel_mismatch.hpp>
+#include <hpx/include/parallel_set_operations.hpp>

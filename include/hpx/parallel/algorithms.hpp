@@ -1353,6 +1353,97 @@ detail::result_t<P, util::tagged_tuple<In1, In2, Out>> merge(P&& p, In1 first1, 
     return detail::finish<R>(p, t, [last1, last2, end] { return R{last1, last2, end}; });
 }
 
+// --------------------------------------------------------- set operations
+// set_union.hpp:47, set_intersection.hpp, set_difference.hpp,
+// set_symmetric_difference.hpp, includes.hpp:129 (exported by
+// hpx/include/parallel_set_operations.hpp): std::set_* / std::includes on
+// sorted ranges as multisets, one pass (hpxhip/kernels/set_kernel.hpp)
+// instead of the reference's chunked std::set_* into a len1 + len2 buffer
+// and a second copy (detail/set_operation.hpp:72-193).  std::less /
+// std::greater run the library's kernels in the key order of sort and merge
+// (floats: IEEE total order, -0.0 and +0.0 are different keys, NaNs with the
+// same bits the same key); any other HPX_HOST_DEVICE comparator runs the same
+// kernel as a device closure (hipcc).  dest must not overlap either input.
+namespace setops {
+template <typename P, typename In1, typename In2, typename T, typename Comp>
+auto call(char const* what, int op, P const& p, detail::hip::target const& t, In1 first1, In1 last1, In2 first2,
+          In2 last2, T* out, Comp const& comp) {
+    static_assert(detail::is_dev<In1> && detail::is_dev<In2>, "set operations: device iterators required");
+    static_assert(std::is_same<T, detail::value_t<In1>>::value && std::is_same<T, detail::value_t<In2>>::value,
+                  "set operations: one element type");
+    auto slot = t.make_result_slot();
+    T const* a = static_cast<T const*>(first1.device_ptr());
+    T const* b = static_cast<T const*>(first2.device_ptr());
+    const uint64_t n1 = detail::distance(first1, last1), n2 = detail::distance(first2, last2);
+    uint64_t* count_dev = static_cast<uint64_t*>(slot.device());
+    if constexpr (detail::is_complete_compare<Comp>) {
+        detail::check(hpxhip_set_operation(detail::dt<T>, op, a, n1, b, n2, out,
+                                           detail::tr::compare_t<Comp>::descending ? 1 : 0, count_dev, t.stream(),
+                                           nullptr, 0),
+                      what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::set_operation(t, op, a, n1, b, n2, out, comp, count_dev);
+#else
+        detail::no_device_mapping<Comp>(what);
+#endif
+    }
+    detail::fetch_slot(t, slot, 8, what);
+    return slot;
+}
+
+template <typename P, typename In1, typename In2, typename Out, typename Comp>
+detail::result_t<P, Out> to_dest(char const* what, int op, P const& p, In1 first1, In1 last1, In2 first2, In2 last2,
+                                 Out dest, Comp const& comp) {
+    static_assert(detail::is_dev<Out>, "set operations: device iterators required");
+    using T = detail::value_t<Out>;
+    auto const& t = detail::target_of(p, first1);
+    auto slot = call(what, op, p, t, first1, last1, first2, last2, static_cast<T*>(dest.device_ptr()), comp);
+    return detail::finish_slot<Out>(p, t, std::move(slot), [dest](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return dest + static_cast<std::ptrdiff_t>(c);
+    });
+}
+}  // namespace setops
+
+template <typename P, typename In1, typename In2, typename Out, typename Comp = std::less<>>
+detail::result_t<P, Out> set_union(P&& p, In1 first1, In1 last1, In2 first2, In2 last2, Out dest,
+                                   Comp&& comp = Comp()) {
+    return setops::to_dest("set_union", HPXHIP_SET_UNION, p, first1, last1, first2, last2, dest, comp);
+}
+template <typename P, typename In1, typename In2, typename Out, typename Comp = std::less<>>
+detail::result_t<P, Out> set_intersection(P&& p, In1 first1, In1 last1, In2 first2, In2 last2, Out dest,
+                                          Comp&& comp = Comp()) {
+    return setops::to_dest("set_intersection", HPXHIP_SET_INTERSECTION, p, first1, last1, first2, last2, dest, comp);
+}
+template <typename P, typename In1, typename In2, typename Out, typename Comp = std::less<>>
+detail::result_t<P, Out> set_difference(P&& p, In1 first1, In1 last1, In2 first2, In2 last2, Out dest,
+                                        Comp&& comp = Comp()) {
+    return setops::to_dest("set_difference", HPXHIP_SET_DIFFERENCE, p, first1, last1, first2, last2, dest, comp);
+}
+template <typename P, typename In1, typename In2, typename Out, typename Comp = std::less<>>
+detail::result_t<P, Out> set_symmetric_difference(P&& p, In1 first1, In1 last1, In2 first2, In2 last2, Out dest,
+                                                  Comp&& comp = Comp()) {
+    return setops::to_dest("set_symmetric_difference", HPXHIP_SET_SYMMETRIC_DIFFERENCE, p, first1, last1, first2,
+                           last2, dest, comp);
+}
+// includes.hpp:129: every value's count in [first2, last2) is at most its
+// count in [first1, last1), i.e. set_difference(range 2, range 1) keeps
+// nothing -- counted without an output; true for an empty second range.
+template <typename P, typename In1, typename In2, typename Comp = std::less<>>
+detail::result_t<P, bool> includes(P&& p, In1 first1, In1 last1, In2 first2, In2 last2, Comp&& comp = Comp()) {
+    using T = detail::value_t<In1>;
+    auto const& t = detail::target_of(p, first1);
+    auto slot = setops::call("includes", HPXHIP_SET_DIFFERENCE, p, t, first2, last2, first1, last1,
+                             static_cast<T*>(nullptr), comp);
+    return detail::finish_slot<bool>(p, t, std::move(slot), [](unsigned char const* b) {
+        uint64_t c;
+        std::memcpy(&c, b, 8);
+        return c == 0;
+    });
+}
+
 }  // namespace algo
 // --------------------------------------------------------------- for_loop
 // for_loop_induction.hpp:210-219: an induction over an iterator, value at
@@ -1762,6 +1853,11 @@ HPXHIP_GUARDED_ALGORITHM(is_sorted)
 HPXHIP_GUARDED_ALGORITHM(sort_by_key)
 HPXHIP_GUARDED_ALGORITHM(reduce_by_key)
 HPXHIP_GUARDED_ALGORITHM(merge)
+HPXHIP_GUARDED_ALGORITHM(set_union)
+HPXHIP_GUARDED_ALGORITHM(set_intersection)
+HPXHIP_GUARDED_ALGORITHM(set_difference)
+HPXHIP_GUARDED_ALGORITHM(set_symmetric_difference)
+HPXHIP_GUARDED_ALGORITHM(includes)
 HPXHIP_GUARDED_ALGORITHM(for_loop_n)
 HPXHIP_GUARDED_ALGORITHM(for_loop)
 HPXHIP_GUARDED_ALGORITHM(for_loop_n_strided)
@@ -1795,6 +1891,11 @@ using parallel::v1::reduction_min;
 using parallel::v1::reduction_multiplies;
 using parallel::v1::reduction_plus;
 using parallel::v1::merge;
+using parallel::v1::set_union;
+using parallel::v1::set_intersection;
+using parallel::v1::set_difference;
+using parallel::v1::set_symmetric_difference;
+using parallel::v1::includes;
 using parallel::v1::inclusive_scan;
 using parallel::v1::reduce;
 using parallel::v1::reduce_by_key;

@@ -51,6 +51,7 @@
 #if HPX_HAVE_HIP_DEVICE_CLOSURES
 #include <hpxhip/kernels/compaction_kernel.hpp>
 #include <hpxhip/kernels/merge_kernel.hpp>
+#include <hpxhip/kernels/set_kernel.hpp>
 #include <hpxhip/kernels/reduce_by_key_kernel.hpp>
 #include <hpxhip/kernels/reduce_kernel.hpp>
 #include <hpxhip/kernels/scan_kernel.hpp>
@@ -425,6 +426,29 @@ void merge_sort(compute::hip::target const& t, T* data, uint64_t n, Comp const& 
     }
     if (src != data) compute::hip::detail::check(hpxhip_memcpy_async(data, src, n * sizeof(T), HPXHIP_D2D, t.stream()), "sort copy-back");
 }
+// ----------------------------------------------------------- set operations
+// set_union.hpp:47 and its siblings, includes.hpp:129 with any comparator:
+// the library's kernels (set_kernel.hpp) through the library's launcher,
+// instantiated for the user's strict weak ordering.  out == nullptr counts.
+template <typename T, typename Comp>
+struct as_less {
+    Comp comp;
+    __device__ __forceinline__ bool operator()(T const& a, T const& b) const { return static_cast<bool>(comp(a, b)); }
+};
+
+template <typename T, typename Comp>
+void set_operation(compute::hip::target const& t, int op, T const* a, uint64_t na, T const* b, uint64_t nb, T* out,
+                   Comp const& comp, uint64_t* count_dev) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "set operation (device closure): 4- or 8-byte element types");
+    namespace S = K::set_detail;
+    void* ws = scratch(t, S::scratch_bytes(na + nb), "set operation scratch");
+    using L = as_less<T, std::decay_t<Comp>>;
+    const hipError_t e = S::launch(a, na, b, nb, out, op, L{comp}, count_dev, ws, error_word(t), stream_of(t));
+    if (e != hipSuccess)
+        throw hpx::kernel_error(static_cast<int>(e),
+                                std::string("set operation (device closure): ") + hipGetErrorString(e));
+}
+
 // ------------------------------------------------------------ search family
 // find.hpp, all_any_none.hpp, count.hpp, minmax.hpp, equal.hpp, mismatch.hpp
 // with any predicate, comparator and projection: the library's kernels

@@ -145,7 +145,8 @@ enum hpxhip_algo {
     HPXHIP_ALGO_UNIQUE_COPY = 10,
     /* 11 is not assigned */
     HPXHIP_ALGO_COUNT_IF = 12,
-    HPXHIP_ALGO_MINMAX_ELEMENT = 13 /* the size for HPXHIP_X_MINMAX, enough for each `which` */
+    HPXHIP_ALGO_MINMAX_ELEMENT = 13, /* the size for HPXHIP_X_MINMAX, enough for each `which` */
+    HPXHIP_ALGO_SET_OPERATION = 14 /* n = n1 + n2 */
 };
 
 typedef struct hpxhip_stream_opaque* hpxhip_stream; /* == hipStream_t */
@@ -508,6 +509,38 @@ int hpxhip_merge(int dtype, const void* in1, uint64_t n1, const void* in2, uint6
    overlap in.  Scratch: HPXHIP_ALGO_MERGE_RUNS with n = the total. */
 int hpxhip_merge_runs(int dtype, const void* in, const uint64_t* run_offsets, int nruns, void* out,
                       int descending, hpxhip_stream stream, void* scratch, size_t scratch_bytes);
+/* ----------------------------------------------------- set operations */
+/* set_union.hpp:47, set_intersection.hpp, set_difference.hpp,
+   set_symmetric_difference.hpp (exported by parallel_set_operations.hpp):
+   std::set_* on the sorted ranges in1[0,n1) and in2[0,n2), as multisets.
+   With cnt1 / cnt2 the elements equivalent to a value in in1 / in2 and k an
+   element's index inside its own range's run of that value, kept are
+     UNION                 in1: all          in2: k >= cnt1
+     INTERSECTION          in1: k < cnt2     in2: none
+     DIFFERENCE            in1: k >= cnt2    in2: none
+     SYMMETRIC_DIFFERENCE  in1: k >= cnt2    in2: k >= cnt1
+   written to out[0, count) in the order of the stable merge (by key, in1
+   before in2 on ties, index order inside a range); *count_dev (uint64,
+   device) receives count and is always written, also for n1 + n2 == 0.
+   out == NULL: count only, nothing else is written -- includes(A, B)
+   (includes.hpp:129) is DIFFERENCE with in1 = B, in2 = A and count == 0.
+   Key order: hpxhip_sort's and hpxhip_merge's (integers as std::less, floats
+   in IEEE total order: -0.0 and +0.0 are different keys, NaNs with the same
+   bits the same key), descending as std::greater.  out must hold the result
+   (at most n1 + n2 elements) and must not overlap the inputs.  One pass: each
+   input is read once, only kept elements are written.  Unsorted input gives
+   an unspecified selection inside out[0, n1 + n2) and may raise the device
+   error word.  Scratch: HPXHIP_ALGO_SET_OPERATION with n = n1 + n2. */
+enum hpxhip_set_op {
+    HPXHIP_SET_UNION = 0,
+    HPXHIP_SET_INTERSECTION = 1,
+    HPXHIP_SET_DIFFERENCE = 2,
+    HPXHIP_SET_SYMMETRIC_DIFFERENCE = 3
+};
+int hpxhip_set_operation(int dtype, int op, const void* in1, uint64_t n1, const void* in2, uint64_t n2,
+                         void* out, int descending, uint64_t* count_dev, hpxhip_stream stream,
+                         void* scratch, size_t scratch_bytes);
+
 /* Batched binary search in a sorted range (the partition cut of the
    segmented sort; std::lower_bound / std::upper_bound semantics under the
    sort's key order): out_dev[i] = number of sorted[] elements ordered before

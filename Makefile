@@ -42,6 +42,9 @@ $(BUILD)/csrc/%.o: hpx_amd/csrc/%.hip $(KHDR)
 
 # search.hip (the search family) is part of reduce.hip's translation unit
 $(BUILD)/csrc/reduce.o: hpx_amd/csrc/search.hip
+# permute.hip (reverse, rotate, swap_ranges, replace, adjacent_difference) is
+# part of elementwise.hip's translation unit
+$(BUILD)/csrc/elementwise.o: hpx_amd/csrc/permute.hip
 
 $(LIB): $(KOBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(KOBJ)
@@ -104,7 +107,7 @@ tests/cxx/bin/oracle_sanitize: tests/cxx/oracle_sanitize.cpp oracle/oracle.cpp o
 
 # ... and the hipcc-compiled ones (device closures, HPX_HOST_DEVICE lambdas)
 HIPT     := device_closures partitioned_vector closure_algorithms closure_timing dataflow_stencil bench_targets \
-            reduce_by_key partition unique search set_operations
+            reduce_by_key partition unique search set_operations permute
 HIPTBIN  := $(HIPT:%=tests/cxx/bin/%)
 HTFLAGS  := -O2 -std=c++17 --offload-arch=$(ARCH) --offload-compress -Wall -Wno-unused-parameter -Iinclude
 

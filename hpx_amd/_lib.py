@@ -158,6 +158,13 @@ SIGNATURES = {
     "hpxhip_transform_strided": [_i, _i, _i, _i, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _u64, _vp],
     "hpxhip_transform_binary_strided": [_i, _i, _i, _i, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, _vp,
                                         ctypes.c_int64, _u64, _vp],
+    "hpxhip_reverse": [_i, _vp, _u64, _vp],
+    "hpxhip_reverse_copy": [_i, _vp, _vp, _u64, _vp],
+    "hpxhip_rotate": [_i, _vp, _u64, _u64, _vp],
+    "hpxhip_rotate_copy": [_i, _vp, _u64, _u64, _vp, _vp],
+    "hpxhip_swap_ranges": [_i, _vp, _vp, _u64, _vp],
+    "hpxhip_replace_if": [_i, _i, _vp, _vp, _vp, _vp, _u64, _vp],
+    "hpxhip_adjacent_difference": [_i, _i, _vp, _vp, _vp, _u64, _vp],
     "hpxhip_transform_reduce": [_i, _i, _i, _i, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_transform_reduce_binary": [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _sz],
     "hpxhip_fold": [_i, _i, _vp, _vp, _u64, _vp, _vp],

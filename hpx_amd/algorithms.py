@@ -33,6 +33,11 @@ calls one whole-algorithm entry point of the C ABI (include/hpxhip.h):
                              the reference's chunked std::set_* into a len1 +
                              len2 buffer and a second copy,
                              detail/set_operation.hpp:72-193)
+  reverse / reverse_copy     reverse.hpp:44-79, 155, 191
+  rotate / rotate_copy       rotate.hpp:57-100, 219-268
+  swap_ranges                swap_ranges.hpp:128
+  replace(_if) / replace_copy(_if)  replace.hpp:164, 326, 493, 683
+  adjacent_difference        adjacent_difference.hpp:99, 194, 275
   find / find_if(_not)       find.hpp:70, 216, 382 (early exit: a hint on the
   all_of / any_of / none_of  result word, all_any_none.hpp)
   count / count_if           count.hpp:259, 451
@@ -864,6 +869,124 @@ def includes(pol, first1, last1, first2, last2, comp=F.less):
     return _finish(is_task, stream, tgt, lambda: count() == 0)
 
 
+# ------------------------------------ rearranging and rewriting a range
+def _permute_ranges(what, pol, first, last, *others):
+    """Argument checks of the rearranging algorithms, all before the first
+    device call -> (stream, tgt, is_task, n).  others: further device
+    iterators of the same dtype (a second range's begin, a destination)."""
+    _exec_of(pol)
+    n = _check_range(first, last)
+    for it in others:
+        if not isinstance(it, iterator):
+            raise TypeError(f"{what}: expected device iterators (hpx_amd.compute.iterator)")
+        if it.dtype != first.dtype:
+            raise TypeError(f"{what}: the ranges must have one dtype")
+    stream, tgt, is_task = _context(pol, first, *others)
+    return stream, tgt, is_task, n
+
+
+def reverse(pol, first, last):
+    """reverse.hpp:44-79: [first, last) reversed in place; returns last (a
+    future under par(task)).  The middle element of an odd range is not
+    written."""
+    stream, tgt, is_task, n = _permute_ranges("reverse", pol, first, last)
+    L.call("hpxhip_reverse", first.dtype, _vp(first.address), n, stream)
+    return _finish(is_task, stream, tgt, lambda: last)
+
+
+def reverse_copy(pol, first, last, dest):
+    """reverse.hpp:155,191: dest[i] = first[n-1-i]; returns (last, dest + n).
+    dest must not overlap the input."""
+    stream, tgt, is_task, n = _permute_ranges("reverse_copy", pol, first, last, dest)
+    L.call("hpxhip_reverse_copy", first.dtype, _vp(first.address), _vp(dest.address), n, stream)
+    return _finish(is_task, stream, tgt, lambda: (last, dest + n))
+
+
+def rotate(pol, first, new_first, last):
+    """rotate.hpp:57-100: left rotation in place, *new_first becomes *first;
+    returns (first + (last - new_first), last).  Two launches: both parts
+    reversed, then the whole range (the reference's rotate_helper)."""
+    _exec_of(pol)
+    mid = _check_range(first, new_first)
+    if mid > _check_range(first, last):
+        raise ValueError("rotate: new_first lies beyond last")
+    stream, tgt, is_task, n = _permute_ranges("rotate", pol, first, last, new_first)
+    L.call("hpxhip_rotate", first.dtype, _vp(first.address), mid, n, stream)
+    return _finish(is_task, stream, tgt, lambda: (first + (n - mid), last))
+
+
+def rotate_copy(pol, first, new_first, last, dest):
+    """rotate.hpp:219-268: dest[i] = first[(i + mid) % n] with mid = new_first
+    - first, both copies in one launch; returns (last, dest + n).  dest must
+    not overlap the input."""
+    _exec_of(pol)
+    mid = _check_range(first, new_first)
+    if mid > _check_range(first, last):
+        raise ValueError("rotate_copy: new_first lies beyond last")
+    stream, tgt, is_task, n = _permute_ranges("rotate_copy", pol, first, last, new_first, dest)
+    L.call("hpxhip_rotate_copy", first.dtype, _vp(first.address), mid, n, _vp(dest.address), stream)
+    return _finish(is_task, stream, tgt, lambda: (last, dest + n))
+
+
+def swap_ranges(pol, first1, last1, first2):
+    """swap_ranges.hpp:128: first1[i] <-> first2[i]; returns first2 + n.  The
+    ranges must not overlap."""
+    stream, tgt, is_task, n = _permute_ranges("swap_ranges", pol, first1, last1, first2)
+    L.call("hpxhip_swap_ranges", first1.dtype, _vp(first1.address), _vp(first2.address), n, stream)
+    return _finish(is_task, stream, tgt, lambda: first2 + n)
+
+
+def _replace_call(what, pol, first, last, dest, pred, new_value):
+    _exec_of(pol)
+    pred = F.require(pred, F.Predicate, what)
+    stream, tgt, is_task, n = _permute_ranges(what, pol, first, last, dest)
+    arg = L.scalar_buf(first.dtype, pred.arg)
+    new = L.scalar_buf(first.dtype, new_value)
+    L.call("hpxhip_replace_if", first.dtype, pred.kind, arg, new, _vp(first.address), _vp(dest.address), n, stream)
+    return stream, tgt, is_task, n
+
+
+def replace_if(pol, first, last, pred, new_value):
+    """replace.hpp:326: x = new_value where pred(x), in place; returns last."""
+    stream, tgt, is_task, _ = _replace_call("replace_if", pol, first, last, first, pred, new_value)
+    return _finish(is_task, stream, tgt, lambda: last)
+
+
+def replace(pol, first, last, old_value, new_value):
+    """replace.hpp:164: replace_if with x == old_value, compared by value: 0.0
+    replaces -0.0 too, a NaN old_value replaces nothing."""
+    stream, tgt, is_task, _ = _replace_call("replace", pol, first, last, first, F.equal_to(old_value), new_value)
+    return _finish(is_task, stream, tgt, lambda: last)
+
+
+def replace_copy_if(pol, first, last, dest, pred, new_value):
+    """replace.hpp:683: dest[i] = pred(x) ? new_value : x; returns
+    (last, dest + n).  dest may be first itself, else it must not overlap."""
+    stream, tgt, is_task, n = _replace_call("replace_copy_if", pol, first, last, dest, pred, new_value)
+    return _finish(is_task, stream, tgt, lambda: (last, dest + n))
+
+
+def replace_copy(pol, first, last, dest, old_value, new_value):
+    """replace.hpp:493: replace_copy_if with x == old_value (by value)."""
+    stream, tgt, is_task, n = _replace_call("replace_copy", pol, first, last, dest, F.equal_to(old_value), new_value)
+    return _finish(is_task, stream, tgt, lambda: (last, dest + n))
+
+
+def adjacent_difference(pol, first, last, dest, op=None):
+    """adjacent_difference.hpp:99,194,275: dest[0] = first[0], dest[i] =
+    op(first[i], first[i-1]); op defaults to F.subtract() (integers wrap,
+    floats are one IEEE operation); returns dest + n.  dest must not overlap
+    the input."""
+    _exec_of(pol)
+    op = F.require(F.subtract() if op is None else op, F.Binary, "adjacent_difference")
+    if op.compute is not None:
+        raise ValueError("adjacent_difference: the operator computes in the element type")
+    stream, tgt, is_task, n = _permute_ranges("adjacent_difference", pol, first, last, dest)
+    sc = L.scalars_buf(first.dtype, op.scalars)
+    L.call("hpxhip_adjacent_difference", first.dtype, op.kind, sc, _vp(first.address), _vp(dest.address), n, stream)
+    return _finish(is_task, stream, tgt, lambda: dest + n)
+
+
 # ------------------------------------------------------------------ for_loop
 class induction:
     """for_loop_induction.hpp:210-219: an induction variable whose value at
@@ -1153,7 +1276,9 @@ for _name in ("generate", "fill", "fill_n", "for_each", "for_each_n", "copy", "c
               "min_element", "max_element", "minmax_element", "equal", "mismatch", "transform",
               "reduce", "transform_reduce", "inclusive_scan", "exclusive_scan", "transform_inclusive_scan",
               "transform_exclusive_scan", "sort", "is_sorted", "sort_by_key", "reduce_by_key", "merge",
-              "set_union", "set_intersection", "set_difference", "set_symmetric_difference", "includes", "for_loop_n",
+              "set_union", "set_intersection", "set_difference", "set_symmetric_difference", "includes",
+              "reverse", "reverse_copy", "rotate", "rotate_copy", "swap_ranges", "replace", "replace_if",
+              "replace_copy", "replace_copy_if", "adjacent_difference", "for_loop_n",
               "for_loop",
               "for_loop_n_strided", "for_loop_strided"):
     if _name in globals():

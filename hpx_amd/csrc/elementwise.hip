@@ -533,3 +533,7 @@ int hpxhip_transform_binary_strided(int in_dtype, int compute_dtype, int out_dty
 }
 
 }  // extern "C"
+
+// reverse, rotate, swap_ranges, replace and adjacent_difference: more
+// streaming kernels over this file's cuts, in this translation unit.
+#include "permute.hip"

@@ -9,3 +9,8 @@
 #include <hpx/include/parallel_minmax.hpp>
 #include <hpx/include/parallel_mismatch.hpp>
 #include <hpx/include/parallel_set_operations.hpp>
+#include <hpx/include/parallel_reverse.hpp>
+#include <hpx/include/parallel_rotate.hpp>
+#include <hpx/include/parallel_swap_ranges.hpp>
+#include <hpx/include/parallel_replace.hpp>
+#include <hpx/include/parallel_adjacent_difference.hpp>

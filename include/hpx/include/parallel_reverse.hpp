@@ -1,0 +1,3 @@
+// hpx/include/parallel_reverse.hpp -- forwards to the HIP backend's algorithm layer.
+#pragma once
+#include <hpx/parallel/algorithms.hpp>

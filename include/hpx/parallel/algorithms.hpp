@@ -31,6 +31,14 @@
 //   minmax_element               minmax.hpp:513-541           -> pair<Iter, Iter>
 //   equal                        equal.hpp:229, 398           -> bool
 //   mismatch                     mismatch.hpp:227, 396        -> pair<Iter1, Iter2>
+//   reverse                      reverse.hpp:44-79            -> BidirIter
+//   reverse_copy                 reverse.hpp:155, 191         -> tagged_pair<in, out>
+//   rotate                       rotate.hpp:57-100            -> tagged_pair<begin, end>
+//   rotate_copy                  rotate.hpp:219-268           -> tagged_pair<in, out>
+//   swap_ranges                  swap_ranges.hpp:128          -> FwdIter2
+//   replace, replace_if          replace.hpp:164, 326         -> FwdIter
+//   replace_copy(_if)            replace.hpp:493, 683         -> tagged_pair<in, out>
+//   adjacent_difference          adjacent_difference.hpp:99, 194, 275 -> FwdIter2
 //
 // Synchronous policies (seq, par, par_unseq) return the value after the
 // target's stream is synchronised (the reference's bulk_sync_execute,
@@ -1444,6 +1452,169 @@ detail::result_t<P, bool> includes(P&& p, In1 first1, In1 last1, In2 first2, In2
     });
 }
 
+// ---------------------------------- rearranging and rewriting a range
+// reverse.hpp:44-79,155,191; rotate.hpp:57-100,219-268; swap_ranges.hpp:128;
+// replace.hpp:164,326,493,683; adjacent_difference.hpp:99,194,275 (exported
+// by hpx/include/parallel_reverse.hpp, parallel_rotate.hpp,
+// parallel_swap_ranges.hpp, parallel_replace.hpp and
+// parallel_adjacent_difference.hpp).  Streaming kernels of the library
+// (hpxhip/kernels/permute_kernel.hpp); two different ranges of one call must
+// not overlap.  A mapped predicate / operator runs the library's kernels; any
+// other HPX_HOST_DEVICE callable runs as a device closure (hipcc).
+template <typename P, typename It>
+detail::result_t<P, It> reverse(P&& p, It first, It last) {
+    static_assert(detail::is_dev<It>, "reverse: device iterators required");
+    using T = detail::value_t<It>;
+    auto const& t = detail::target_of(p, first);
+    detail::check(hpxhip_reverse(detail::dt<T>, first.device_ptr(), detail::distance(first, last), t.stream()),
+                  "reverse");
+    return detail::finish<It>(p, t, [last] { return last; });
+}
+
+template <typename P, typename In, typename Out>
+detail::result_t<P, util::tagged_pair<In, Out>> reverse_copy(P&& p, In first, In last, Out dest) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out>, "reverse_copy: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out>>::value, "reverse_copy: element types must match");
+    using R = util::tagged_pair<In, Out>;
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last);
+    detail::check(hpxhip_reverse_copy(detail::dt<T>, first.device_ptr(), dest.device_ptr(), n, t.stream()),
+                  "reverse_copy");
+    Out end = dest + static_cast<std::ptrdiff_t>(n);
+    return detail::finish<R>(p, t, [last, end] { return R{last, end}; });
+}
+
+// rotate.hpp:57-100 -> tagged_pair<begin, end> = (first + (last - new_first), last)
+template <typename P, typename It>
+detail::result_t<P, util::tagged_pair<It, It>> rotate(P&& p, It first, It new_first, It last) {
+    static_assert(detail::is_dev<It>, "rotate: device iterators required");
+    using T = detail::value_t<It>;
+    using R = util::tagged_pair<It, It>;
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last), mid = detail::distance(first, new_first);
+    detail::check(hpxhip_rotate(detail::dt<T>, first.device_ptr(), mid, n, t.stream()), "rotate");
+    It b = first + (last - new_first);
+    return detail::finish<R>(p, t, [b, last] { return R{b, last}; });
+}
+
+template <typename P, typename In, typename Out>
+detail::result_t<P, util::tagged_pair<In, Out>> rotate_copy(P&& p, In first, In new_first, In last, Out dest) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out>, "rotate_copy: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out>>::value, "rotate_copy: element types must match");
+    using R = util::tagged_pair<In, Out>;
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last), mid = detail::distance(first, new_first);
+    detail::check(hpxhip_rotate_copy(detail::dt<T>, first.device_ptr(), mid, n, dest.device_ptr(), t.stream()),
+                  "rotate_copy");
+    Out end = dest + static_cast<std::ptrdiff_t>(n);
+    return detail::finish<R>(p, t, [last, end] { return R{last, end}; });
+}
+
+template <typename P, typename It1, typename It2>
+detail::result_t<P, It2> swap_ranges(P&& p, It1 first1, It1 last1, It2 first2) {
+    static_assert(detail::is_dev<It1> && detail::is_dev<It2>, "swap_ranges: device iterators required");
+    using T = detail::value_t<It1>;
+    static_assert(std::is_same<T, detail::value_t<It2>>::value, "swap_ranges: element types must match");
+    auto const& t = detail::target_of(p, first1);
+    const uint64_t n = detail::distance(first1, last1);
+    detail::check(hpxhip_swap_ranges(detail::dt<T>, first1.device_ptr(), first2.device_ptr(), n, t.stream()),
+                  "swap_ranges");
+    It2 end = first2 + static_cast<std::ptrdiff_t>(n);
+    return detail::finish<It2>(p, t, [end] { return end; });
+}
+
+namespace permute {
+// out[i] = f(in[i]) ? nv : in[i], queued on t's stream; out may be in
+template <typename T, typename F>
+void replace_call(char const* what, detail::hip::target const& t, T const* in, T* out, uint64_t n, F const& f,
+                  T nv) {
+    if constexpr (detail::is_complete_pred<F>) {
+        using Tr = detail::tr::pred_t<F>;
+        T arg = static_cast<T>(Tr::arg(f));
+        detail::check(hpxhip_replace_if(detail::dt<T>, Tr::kind, &arg, &nv, in, out, n, t.stream()), what);
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::replace_if(t, in, out, n, f, nv);
+#else
+        detail::no_device_mapping<F>(what);
+#endif
+    }
+}
+}  // namespace permute
+
+template <typename P, typename It, typename F, typename V>
+detail::result_t<P, It> replace_if(P&& p, It first, It last, F&& f, V const& new_value) {
+    static_assert(detail::is_dev<It>, "replace_if: device iterators required");
+    using T = detail::value_t<It>;
+    auto const& t = detail::target_of(p, first);
+    permute::replace_call<T>("replace_if", t, first.device_ptr(), first.device_ptr(), detail::distance(first, last),
+                             f, static_cast<T>(new_value));
+    return detail::finish<It>(p, t, [last] { return last; });
+}
+
+// replace.hpp:164: x == old_value by value (HPXHIP_P_EQ): 0.0 replaces -0.0
+// too, a NaN old_value replaces nothing.
+template <typename P, typename It, typename V1, typename V2>
+detail::result_t<P, It> replace(P&& p, It first, It last, V1 const& old_value, V2 const& new_value) {
+    using T = detail::value_t<It>;
+    return replace_if(std::forward<P>(p), first, last,
+                      compute::hip::functional::equal_to<T>{static_cast<T>(old_value)}, new_value);
+}
+
+template <typename P, typename In, typename Out, typename F, typename V>
+detail::result_t<P, util::tagged_pair<In, Out>> replace_copy_if(P&& p, In first, In last, Out dest, F&& f,
+                                                                V const& new_value) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out>, "replace_copy_if: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out>>::value, "replace_copy_if: element types must match");
+    using R = util::tagged_pair<In, Out>;
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last);
+    permute::replace_call<T>("replace_copy_if", t, first.device_ptr(), dest.device_ptr(), n, f,
+                             static_cast<T>(new_value));
+    Out end = dest + static_cast<std::ptrdiff_t>(n);
+    return detail::finish<R>(p, t, [last, end] { return R{last, end}; });
+}
+
+template <typename P, typename In, typename Out, typename V1, typename V2>
+detail::result_t<P, util::tagged_pair<In, Out>> replace_copy(P&& p, In first, In last, Out dest, V1 const& old_value,
+                                                             V2 const& new_value) {
+    using T = detail::value_t<In>;
+    return replace_copy_if(std::forward<P>(p), first, last, dest,
+                           compute::hip::functional::equal_to<T>{static_cast<T>(old_value)}, new_value);
+}
+
+// adjacent_difference.hpp:99,194,275: dest[0] = first[0], dest[i] =
+// op(first[i], first[i-1]) -> dest + n.  std::minus (the default) wraps on
+// integers and is one IEEE operation on floats.
+template <typename P, typename In, typename Out, typename Op = std::minus<>>
+detail::result_t<P, Out> adjacent_difference(P&& p, In first, In last, Out dest, Op&& op = Op()) {
+    static_assert(detail::is_dev<In> && detail::is_dev<Out>, "adjacent_difference: device iterators required");
+    using T = detail::value_t<In>;
+    static_assert(std::is_same<T, detail::value_t<Out>>::value, "adjacent_difference: element types must match");
+    auto const& t = detail::target_of(p, first);
+    const uint64_t n = detail::distance(first, last);
+    T const* in = first.device_ptr();
+    T* out = dest.device_ptr();
+    if constexpr (detail::is_complete_binary<Op>) {
+        using Tr = detail::tr::binary_t<Op>;
+        T s[2] = {};
+        Tr::scalars(op, s);
+        detail::check(hpxhip_adjacent_difference(detail::dt<T>, Tr::kind, s, in, out, n, t.stream()),
+                      "adjacent_difference");
+    } else {
+#if HPX_HAVE_HIP_DEVICE_CLOSURES
+        detail::dev::adjacent_difference(t, in, out, n, op);
+#else
+        detail::no_device_mapping<Op>("adjacent_difference");
+#endif
+    }
+    Out end = dest + static_cast<std::ptrdiff_t>(n);
+    return detail::finish<Out>(p, t, [end] { return end; });
+}
+
 }  // namespace algo
 // --------------------------------------------------------------- for_loop
 // for_loop_induction.hpp:210-219: an induction over an iterator, value at
@@ -1858,6 +2029,16 @@ HPXHIP_GUARDED_ALGORITHM(set_intersection)
 HPXHIP_GUARDED_ALGORITHM(set_difference)
 HPXHIP_GUARDED_ALGORITHM(set_symmetric_difference)
 HPXHIP_GUARDED_ALGORITHM(includes)
+HPXHIP_GUARDED_ALGORITHM(reverse)
+HPXHIP_GUARDED_ALGORITHM(reverse_copy)
+HPXHIP_GUARDED_ALGORITHM(rotate)
+HPXHIP_GUARDED_ALGORITHM(rotate_copy)
+HPXHIP_GUARDED_ALGORITHM(swap_ranges)
+HPXHIP_GUARDED_ALGORITHM(replace)
+HPXHIP_GUARDED_ALGORITHM(replace_if)
+HPXHIP_GUARDED_ALGORITHM(replace_copy)
+HPXHIP_GUARDED_ALGORITHM(replace_copy_if)
+HPXHIP_GUARDED_ALGORITHM(adjacent_difference)
 HPXHIP_GUARDED_ALGORITHM(for_loop_n)
 HPXHIP_GUARDED_ALGORITHM(for_loop)
 HPXHIP_GUARDED_ALGORITHM(for_loop_n_strided)
@@ -1896,6 +2077,16 @@ using parallel::v1::set_intersection;
 using parallel::v1::set_difference;
 using parallel::v1::set_symmetric_difference;
 using parallel::v1::includes;
+using parallel::v1::reverse;
+using parallel::v1::reverse_copy;
+using parallel::v1::rotate;
+using parallel::v1::rotate_copy;
+using parallel::v1::swap_ranges;
+using parallel::v1::replace;
+using parallel::v1::replace_if;
+using parallel::v1::replace_copy;
+using parallel::v1::replace_copy_if;
+using parallel::v1::adjacent_difference;
 using parallel::v1::inclusive_scan;
 using parallel::v1::reduce;
 using parallel::v1::reduce_by_key;

@@ -23,6 +23,8 @@
 //                              search_kernel.hpp   (first hit by atomic min with
 //                                                   an early-exit hint; arg-extreme
 //                                                   pairs; count on the reduce kernel)
+//   replace_if, replace_copy_if, adjacent_difference
+//                              device_closures.hpp (the transform closure kernels)
 //   sort (comp, proj)          merge_kernel.hpp    (block sort in LDS, then
 //                                                   merge-path passes)
 //
@@ -41,6 +43,7 @@
 #include <hpx/compute/hip.hpp>
 #include <hpx/compute/hip/detail/launch.hpp>
 #include <hpx/compute/hip/functional.hpp>
+#include <hpx/parallel/detail/device_closures.hpp>
 
 #include <algorithm>
 #include <atomic>
@@ -447,6 +450,55 @@ void set_operation(compute::hip::target const& t, int op, T const* a, uint64_t n
     if (e != hipSuccess)
         throw hpx::kernel_error(static_cast<int>(e),
                                 std::string("set operation (device closure): ") + hipGetErrorString(e));
+}
+
+// -------------------------------------------- replace_if, adjacent_difference
+// replace.hpp:326,683 with any predicate and adjacent_difference.hpp:194,275
+// with any binary operation: the closure kernels of transform
+// (device_closures.hpp) with the callable wrapped.  out may be exactly in for
+// replace_if; adjacent_difference reads in[i] and in[i-1] as two ranges offset
+// by one element, the first element is a one-element copy.  The overlaps the
+// C ABI refuses are refused here the same way (INVALID_ARGUMENT, before any
+// launch).
+// [a, a + n) and [b, b + n) share a byte: the C ABI's refusal (permute.hip),
+// made here too because these calls do not pass through it
+template <typename T>
+bool ranges_overlap(T const* a, T const* b, uint64_t n) {
+    const std::uintptr_t x = reinterpret_cast<std::uintptr_t>(a), y = reinterpret_cast<std::uintptr_t>(b);
+    const unsigned __int128 len = static_cast<unsigned __int128>(n) * sizeof(T);
+    return x < y + len && y < x + len;
+}
+
+template <typename T, typename Pred>
+struct replace_where {
+    Pred pred;
+    T nv;
+    __device__ __forceinline__ T operator()(T const& x) const { return static_cast<bool>(pred(x)) ? nv : x; }
+};
+
+template <typename T, typename Pred>
+void replace_if(compute::hip::target const& t, T const* in, T* out, uint64_t n, Pred const& pred, T nv) {
+    if (n == 0) return;
+    if (in != out && ranges_overlap(in, static_cast<T const*>(out), n))
+        compute::hip::detail::check(HPXHIP_ERROR_INVALID_ARGUMENT, "replace_if (device closure): ranges overlap");
+    device_transform(t, replace_where<T, std::decay_t<Pred>>{pred, nv}, in, out, n);
+}
+
+template <typename T, typename Op>
+struct as_difference {
+    Op op;
+    __device__ __forceinline__ T operator()(T const& x, T const& y) const { return static_cast<T>(op(x, y)); }
+};
+
+template <typename T, typename Op>
+void adjacent_difference(compute::hip::target const& t, T const* in, T* out, uint64_t n, Op const& op) {
+    if (n == 0) return;
+    if (ranges_overlap(in, static_cast<T const*>(out), n))
+        compute::hip::detail::check(HPXHIP_ERROR_INVALID_ARGUMENT,
+                                    "adjacent_difference (device closure): ranges overlap");
+    compute::hip::detail::check(hpxhip_copy(compute::hip::dtype_of<T>::value, in, out, 1, t.stream()),
+                                "adjacent_difference (device closure)");
+    if (n > 1) device_transform2(t, as_difference<T, std::decay_t<Op>>{op}, in + 1, in, out + 1, n - 1);
 }
 
 // ------------------------------------------------------------ search family

@@ -163,6 +163,13 @@ struct tagged_pair {
     B out() const { return second; }
     A in1() const { return first; }
     B in2() const { return second; }
+    // tagged_pair<begin, end> of rotate (rotate.hpp:57).  This mirror keeps
+    // one pair type with every tag's accessor (in / out, in1 / in2 above)
+    // instead of the reference's tag types, so these exist on every pair;
+    // they are meant for rotate's result only: (first + (last - new_first),
+    // last), not a range to iterate over.
+    A begin() const { return first; }
+    B end() const { return second; }
 };
 template <typename A, typename B, typename C>
 struct tagged_tuple {

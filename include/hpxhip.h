@@ -30,6 +30,9 @@
  *   - copy_if                   -> copy.hpp:401-494
  *   - find / count / min_element / equal / mismatch -> find.hpp:70-382,
  *       count.hpp:259,451, minmax.hpp:46-541, equal.hpp:229, mismatch.hpp:227
+ *   - reverse / rotate / swap_ranges / replace / adjacent_difference ->
+ *       reverse.hpp:44-191, rotate.hpp:57-268, swap_ranges.hpp:128,
+ *       replace.hpp:164-683, adjacent_difference.hpp:99-275
  *   - sort / sort_by_key        -> sort.hpp:182-276, sort_by_key.hpp:42-78
  *   - 1d_stencil heat step      -> examples/1d_stencil/1d_stencil_1.cpp:41-72,
  *       1d_stencil_4_parallel.cpp:87-118
@@ -308,6 +311,52 @@ int hpxhip_transform_binary_strided(int in_dtype, int compute_dtype, int out_dty
                                     const void* scalars, const void* in1, int64_t in1_stride,
                                     const void* in2, int64_t in2_stride, void* out,
                                     int64_t out_stride, uint64_t n, hpxhip_stream stream);
+
+/* ------------------------------------- rearranging / rewriting a range */
+/* reverse.hpp, rotate.hpp, swap_ranges.hpp, replace.hpp and
+   adjacent_difference.hpp.  Common to the seven calls below: all six dtypes;
+   n == 0 returns 0 and touches nothing; no scratch.  Checked on the host
+   before any device call, HPXHIP_ERROR_INVALID_ARGUMENT: an unknown dtype or
+   kind, a NULL pointer with n > 0, a pointer that is not aligned to the
+   element, mid > n, and ranges that overlap where the call names it (the
+   standard's parallel overloads require disjoint ranges).  Pointers need no
+   other alignment: ranges at any element offset keep the 16-B kernels. */
+/* reverse.hpp:44-79: data[i] <-> data[n-1-i] for i < n/2; the middle element
+   of an odd range is not written. */
+int hpxhip_reverse(int dtype, void* data, uint64_t n, hpxhip_stream stream);
+/* reverse.hpp:155,191: out[i] = in[n-1-i].  in and out must not overlap. */
+int hpxhip_reverse_copy(int dtype, const void* in, void* out, uint64_t n, hpxhip_stream stream);
+/* rotate.hpp:57-100: left rotation in place, data[mid] becomes data[0]
+   (new[i] = old[(i + mid) % n]).  mid == 0 or mid == n launches nothing;
+   mid > n is INVALID_ARGUMENT.  Built as the reference's rotate_helper
+   (:68-100) from reversals: [0, mid) and [mid, n) reversed in one launch,
+   then [0, n) -- two launches, 4 n sizeof(T) bytes. */
+int hpxhip_rotate(int dtype, void* data, uint64_t mid, uint64_t n, hpxhip_stream stream);
+/* rotate.hpp:219-268: out[i] = in[(i + mid) % n]: the copies in[mid, n) ->
+   out[0, n-mid) and in[0, mid) -> out[n-mid, n) in one launch.  mid > n is
+   INVALID_ARGUMENT; in and out must not overlap. */
+int hpxhip_rotate_copy(int dtype, const void* in, uint64_t mid, uint64_t n, void* out, hpxhip_stream stream);
+/* swap_ranges.hpp:128: a[i] <-> b[i].  a and b must not overlap. */
+int hpxhip_swap_ranges(int dtype, void* a, void* b, uint64_t n, hpxhip_stream stream);
+/* replace.hpp:164 (replace), 326 (replace_if), 493 (replace_copy), 683
+   (replace_copy_if): out[i] = pred(in[i]) ? *new_value : in[i], pred an
+   hpxhip_pred kind against *pred_arg with copy_if's meaning (pred_arg and
+   new_value: host pointers to one dtype element).  replace(old) is
+   HPXHIP_P_EQ, compared by value: 0.0 replaces -0.0, a NaN old replaces
+   nothing.  *new_value is written bitwise (it may be a NaN).  out may be
+   exactly in (the in-place forms); any other overlap is INVALID_ARGUMENT.
+   HPXHIP_P_BITS on a float dtype: HPXHIP_ERROR_UNSUPPORTED. */
+int hpxhip_replace_if(int dtype, int pred_kind, const void* pred_arg, const void* new_value,
+                      const void* in, void* out, uint64_t n, hpxhip_stream stream);
+/* adjacent_difference.hpp:99,194,275: out[0] = in[0], out[i] = op(in[i],
+   in[i-1]) with op an hpxhip_binary kind (x = in[i], y = in[i-1]; scalars: s0
+   of the dtype for TRIAD / AXPY, else may be NULL).  HPXHIP_B_SUB is
+   std::adjacent_difference: integers wrap, floats are one IEEE operation
+   (bit-exact), so it inverts hpxhip_scan's inclusive PLUS on integers.  in
+   and out must not overlap (also not in == out).  One launch; in is read
+   once from memory. */
+int hpxhip_adjacent_difference(int dtype, int binary_kind, const void* scalars,
+                               const void* in, void* out, uint64_t n, hpxhip_stream stream);
 
 /* --------------------------------------------------------- reductions */
 /* transform_reduce.hpp:254: *out_dev = init (op) conv(in[0]) (op) ... (op) conv(in[n-1]),

@@ -1411,21 +1411,30 @@ __global__ __launch_bounds__(THREADS, MINW)  // 4 waves per SIMD: one 1024- or t
         mm = seg[2 * bk + 1] - b;
     }
     const uint32_t m = static_cast<uint32_t>(mm);
-    if (m < 2) return;
+    if (m == 0) return;
+    U* gkeys = keys + b;
+    // r06: a bucket of the padded second pass is read from its slot
+    // (k_pad_scatter) and written to its place in the keys.  This kernel is
+    // the only step that moves it there, so every way out below that skips
+    // the write-back at the end -- one key, all keys equal -- copies the
+    // bucket first (the one-pass form's hand-off leaves it to the two-pass
+    // launch, which reads the same slot).
+    const U* gsrc = gkeys;
+    if (!HAS_VAL && BOUNDS && pad) {
+        const int32_t pc = *pad_cap;
+        if (pc > 0) gsrc = pad + static_cast<uint64_t>(bk) * static_cast<uint32_t>(pc);
+    }
+    if (m < 2) {
+        if constexpr (!HAS_VAL && BOUNDS)
+            if (gsrc != gkeys && t == 0) gkeys[0] = gsrc[0];
+        return;
+    }
 
     const uint32_t wbase = static_cast<uint32_t>(wave) * CHUNK;
     const uint32_t have = m > wbase ? m - wbase : 0u;
     const int nfull = static_cast<int>(have >= static_cast<uint32_t>(CHUNK) ? ITEMS : have / kWave);
     const uint64_t tail_mask = (have % kWave) ? (~0ull >> (kWave - have % kWave)) : 0ull;
     auto active = [&](int r) -> uint64_t { return r < nfull ? ~0ull : (r == nfull ? tail_mask : 0ull); };
-    U* gkeys = keys + b;
-    // r06: a bucket of the padded second pass is read from its slot
-    // (k_pad_scatter) and written to its place in the keys
-    const U* gsrc = gkeys;
-    if (!HAS_VAL && BOUNDS && pad) {
-        const int32_t pc = *pad_cap;
-        if (pc > 0) gsrc = pad + static_cast<uint64_t>(bk) * static_cast<uint32_t>(pc);
-    }
     U* lkeys = s_keys + wbase;
     VAL* gvals = HAS_VAL ? vals + b : nullptr;
     VAL* lvals = s_vals + (HAS_VAL ? wbase : 0);
@@ -1474,7 +1483,20 @@ __global__ __launch_bounds__(THREADS, MINW)  // 4 waves per SIMD: one 1024- or t
                                                : __builtin_clz(static_cast<uint32_t>(diff)));
         top = hb > top ? hb : top;
     }
-    if (top <= 0) return;  // all keys equal
+    if (top <= 0) {  // all keys equal: in order as they are
+        if constexpr (!HAS_VAL && BOUNDS) {
+            // ... but still in their slot (padded pass).  A second read of
+            // the slot, not stores from k[]: those cost the one-pass form one
+            // or two VGPRs and 36 spilled SGPRs (2^30 u32: 9.61 -> 9.78 ms),
+            // the two-pass form 10 to 20 VGPRs (5 -> 4 waves per SIMD with
+            // 64-bit keys) and the 18-key forms, which never get a slot, 140
+            // B of scratch per lane; this loop leaves every instantiation's
+            // VGPRs, scratch and occupancy as they were
+            if (gsrc != gkeys)
+                for (uint32_t i = t; i < m; i += THREADS) st_stream(&gkeys[i], gsrc[i]);
+        }
+        return;
+    }
 
     // ---- the one-pass form (ONEB, see above)
     if constexpr (ONEB > 0) {

@@ -281,6 +281,59 @@ def test_sort_2p30_element_exact(pol, gpu_target, kdt, logn, desc):
     keys.free()
 
 
+@pytest.mark.parametrize("kdt", [np.uint64, np.uint32])
+def test_sort_2p29_all_equal_buckets_padded(pol, gpu_target, kdt, monkeypatch):
+    """Buckets of EQUAL keys in the padded second prefix pass: 2^29 keys
+    taking 2^17 values v << (bits - 17) -- small ids in the high bits --,
+    key i = ((A i + B) mod 2^17) << (bits - 17), so every value occurs 4096
+    times and sorted position j holds (j >> 12) << (bits - 17).
+
+    By the planner (sort.hip k_sort_plan; tests/sort_plan_model.py restates
+    it, but would need the 2^29 keys on the host): live bytes P-1, P-2, P-3
+    (bit bits-17 lies in byte P-3); top-9 digit = v >> 8, 2^20 keys each; the
+    field is (v & 255) << 1, 256 bins of 2^21; b2 <= 7 groups four or more
+    bins (est >= 8192: no fit), b2 = 8 gives est = 2^20 * 2^21 / 2^29 = 4096,
+    4096 + 5 * 64 <= 4608; no joint cell over 4608 * 32; cap = (4096 + 448 + 1
+    + 63) & ~63 = 4608; nb * cap = 2^17 * 4608 = 604 M <= pad_keys = 671 M:
+    the padded pass, each bucket one value's 4096 keys.  s2 = bits - 17 and no
+    bit under it varies, so top_single = 0: k_bucket_sort finds `top <= 0` in
+    every bucket and, before the fix, returned without writing the bucket
+    from its slot to the keys -- the output was the stale buffer (536866816
+    of the 536870912 positions wrong, u64 and u32 alike).  2^29 is the
+    smallest such n (at 2^28 byte P-3 is dead: the LSD)."""
+    import torch
+    monkeypatch.delenv("HPXHIP_SORT_HYBRID", raising=False)
+    dev = torch.device("cuda", gpu_target.device)
+    n = 1 << 29
+    isz = np.dtype(kdt).itemsize
+    shift = 8 * isz - 17
+    tdt = torch.int64 if isz == 8 else torch.int32
+
+    def narrow(x):  # int64 bit patterns -> the key width
+        return x if isz == 8 else (x - ((x >> 31) & 1) * (1 << 32)).to(torch.int32)
+
+    keys = hpx.vector(n, dtype=kdt, tgt=gpu_target)
+    torch.cuda.synchronize(dev)
+    for lo in range(0, n, _CHUNK):
+        i = torch.arange(lo, lo + _CHUNK, dtype=torch.int64, device=dev)
+        h = narrow(((i * _PERM_A + _PERM_B) & ((1 << 17) - 1)) << shift)
+        torch.cuda.synchronize(dev)
+        L.call("hpxhip_memcpy_async", ctypes.c_void_p(keys.data() + lo * isz), ctypes.c_void_p(h.data_ptr()),
+               h.numel() * isz, L.D2D, gpu_target.stream)
+        gpu_target.synchronize()
+    P.sort(pol, keys.begin(), keys.end())
+    got = torch.empty(_CHUNK, dtype=tdt, device=dev)
+    wrong = 0
+    for lo in range(0, n, _CHUNK):
+        L.call("hpxhip_memcpy_async", ctypes.c_void_p(got.data_ptr()), ctypes.c_void_p(keys.data() + lo * isz),
+               _CHUNK * isz, L.D2D, gpu_target.stream)
+        gpu_target.synchronize()
+        j = torch.arange(lo, lo + _CHUNK, dtype=torch.int64, device=dev)
+        wrong += int((got != narrow((j >> 12) << shift)).sum())
+    keys.free()
+    assert wrong == 0, f"{wrong} of {n} positions hold another key than the sorted order's"
+
+
 def test_fp_scan_reproducible_2p30(pol, gpu_target):
     """The fixed-association look-back at the benchmark's size (configs[1]
     names double): two inclusive scans of the same 2^30 mixed-sign doubles,
